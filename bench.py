@@ -2,6 +2,7 @@
 """Throughput bench of the GS hologram loop on MI355X (BASELINE.json configs).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size 1024] [--batch-per-gpu 1] [--iters 200]
+                    [--dump-outputs DIR] [--full]
 
 One *step* is one full GS run (setup + `iters` iterations + phase extraction)
 over this rank's batch of synthetic targets already resident in HBM, followed
@@ -17,12 +18,21 @@ No torch in the ranks: the control plane (RCCL unique-id hand-off, barriers,
 the max of per-rank times) is parallel.Group (stdlib TCP), the data path is
 libslm_hip.so -- its kernels and its RCCL send/recv gather over xGMI.
 
-Rank 0 prints ONE JSON line with the metric, a roofline object for the
+A plain run sets up, warms up, times the K steps and rank 0 prints ONE JSON
+line with the metric (`value`, `ms_per_step`, the configuration). With
+--dump-outputs DIR rank 0 also writes what the last timed step computed, the
+gathered phases (`phase.npy`, float32) and every hologram's error curve
+(`error.npy`, float64), into DIR: the targets are seeded, so two builds run
+with the same arguments can be compared array for array.
+
+--full adds everything else to that line: a sanity check of the gathered
+phases and error curves, a roofline object for the
 dominant kernel (HIP-event timing of every launch of a separately replayed,
 identical run; SURVEY.md 8d byte model and the fused kernels' physical bytes,
 both labelled) and the CPU baseline (the repo's NumPy oracle, 1 core and all
 cores of the host share, on a bounded sample of the same workload, rank 0 at
-N=1 only).
+N=1 only), the secondary configurations and the warm-start parity of the timed
+configuration (--no-extra / --no-cpu-baseline drop those legs of a --full run).
 """
 from __future__ import annotations
 
@@ -43,6 +53,7 @@ from spatial_light_modulator_module_amd import _lib, parallel  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 METRIC = json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+DUMP_BUDGET = 60_000_000  # bytes --dump-outputs writes at most, over all its arrays
 
 
 def parse():
@@ -53,8 +64,14 @@ def parse():
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--batch-per-gpu", type=int, default=1)
     ap.add_argument("--iters", type=int, default=200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the 4096^2 / batched secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (gathered phases, error curves) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline value: output sanity check, "
+                         "per-kernel roofline, per-rank diagnostics, secondary configurations, parity, CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the 4096^2 / batched secondary measurements and the parity run")
     ap.add_argument("--cpu-sample-seconds", type=float, default=20.0)
     return ap.parse_args()
 
@@ -70,6 +87,23 @@ def launch_ranks(n: int) -> int:
         procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env))
     rcs = [p.wait() for p in procs]
     return max(abs(rc) for rc in rcs)
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """Write each array as path/<name>.npy (float32 / float64 as computed). An
+    array over its share of DUMP_BUDGET is cut to a fixed sample: the elements
+    at sorted indices drawn by default_rng(0) for its size, the same in every run."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET // len(arrays)
+    written = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        keep = share // a.itemsize
+        if a.size > keep:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, keep))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = {"shape": list(a.shape), "dtype": str(a.dtype)}
+    return written
 
 
 def targets(first: int, count: int, n: int, w: int | None = None) -> np.ndarray:
@@ -466,8 +500,48 @@ def main():
     value = total_holo / elapsed
     ms_per_step = elapsed / opt.steps * 1e3
 
-    dom, rows, ev_us, _ = kernel_roofline(plan, iters)
     info = plan.info()
+    prec = info["precision"]  # butterflies / twiddles / exchanges; HBM state is complex64
+    out = {
+        "metric": METRIC, "value": round(value, 3), "unit": "holograms/s", "n_gpus": world,
+        "steps": opt.steps, "warmup": opt.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": prec,
+        "data": "synthetic (uniform[0,255) float32 targets, default_rng(1234+b))",
+        "config": {"workload": f"GS {n}x{n}, {iters} iterations, {bper} hologram(s) per GPU, float32 target, "
+                               "uniform incoming intensity, tolerance 0 (BASELINE.json configs[1])",
+                   "height": n, "width": n, "iters": iters, "batch_per_gpu": bper, "global_batch": bper * world,
+                   "parallelism": f"dp{world} (independent holograms; RCCL gather of phases to rank 0)",
+                   "storage": "complex64 field, float32 target/phase", "col_tile": info},
+        "gs_iter_ms": round(ms_per_step / iters, 5),
+    }
+    if opt.dump_outputs:
+        # what the last timed step left on the plans, before anything else runs on
+        # them: every hologram's phase and error curve, gathered to rank 0's host
+        gathered = np.empty((bper * world, n, n), np.float32) if rank == 0 else None
+        plan.gather_phase(counts, root=0, host_out=gathered)
+        stats, _ = plan.gather_stats(counts, root=0, want=rank == 0)
+        if rank == 0:
+            dumped = dump_outputs(opt.dump_outputs, {"phase": gathered, "error": stats[:, :iters, 3]})
+    if opt.full:
+        full_report(opt, group, plan, counts, rank, out, ms_per_step, local_elapsed, device_step_ms)
+    if rank == 0:
+        if opt.dump_outputs:
+            out["outputs"] = dumped
+        if opt.full:
+            out["summary"] = summary(out)  # last: inside the driver's tail of the line
+        print(json.dumps(out), flush=True)
+    plan.close()
+    if world > 1:
+        _lib.comm_destroy()
+    group.close()
+
+
+def full_report(opt, group, plan, counts, rank, out, ms_per_step, local_elapsed, device_step_ms):
+    """Everything a --full run measures and checks beside the headline value,
+    added to rank 0's result line `out` (collective: every rank calls this)."""
+    world, n, bper, iters = len(counts), opt.size, opt.batch_per_gpu, opt.iters
+    info, prec = out["config"]["col_tile"], out["dtype"]
+    dom, rows, ev_us, _ = kernel_roofline(plan, iters)
     diag = rank_diagnostics(plan, counts, rank, local_elapsed, opt.steps, rows)
     # Kernel time inside the timed region: the per-launch events of the separate
     # timed run, scaled by (device time of one step of the timed region, gather
@@ -497,13 +571,8 @@ def main():
     ok = group.bcast(ok)
 
     if rank != 0:
-        plan.close()
-        if world > 1:
-            _lib.comm_destroy()
-        group.close()
         return
 
-    prec = info["precision"]  # butterflies / twiddles / exchanges; HBM state is complex64
     key = f"gs_{n}x{n}_b{bper}_it{iters}_{prec}"
     traffic = traffic_for_plan(pmc_traffic(key), info)
     dr = rows[dom]
@@ -550,21 +619,9 @@ def main():
                                "frac_from_profile": round(dr["model_bytes_per_launch"] / (pk["avg_us_all"] * 1e-6)
                                                           / 1e9 / HBM_PEAK_GBS, 4)
                                if pk.get("avg_us_all") else None}
-    out = {
-        "metric": METRIC, "value": round(value, 3), "unit": "holograms/s", "n_gpus": world,
-        "steps": opt.steps, "warmup": opt.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": prec,
-        "data": "synthetic (uniform[0,255) float32 targets, default_rng(1234+b))",
-        "config": {"workload": f"GS {n}x{n}, {iters} iterations, {bper} hologram(s) per GPU, float32 target, "
-                               "uniform incoming intensity, tolerance 0 (BASELINE.json configs[1])",
-                   "height": n, "width": n, "iters": iters, "batch_per_gpu": bper, "global_batch": bper * world,
-                   "parallelism": f"dp{world} (independent holograms; RCCL gather of phases to rank 0)",
-                   "storage": "complex64 field, float32 target/phase", "col_tile": info},
-        "gs_iter_ms": round(ms_per_step / iters, 5),
-        "roofline": roofline,
-        "check": "ok" if ok else "FAILED",
-        "ranks": ranks,
-    }
+    out["roofline"] = roofline
+    out["check"] = "ok" if ok else "FAILED"
+    out["ranks"] = ranks
     if world == 1 and not opt.no_extra:
         extra = {"pcie_inclusive": pcie_inclusive(plan, targets(0, bper, n), iters)}
         try:  # every line at its BASELINE.json config's own iteration count
@@ -594,12 +651,6 @@ def main():
         out["cpu_baseline"] = cpu_baseline(n, iters, opt.cpu_sample_seconds)
         out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(n, iters, opt.cpu_sample_seconds / 2)
         out["cpu_baseline_configs0"] = cpu_baseline_configs0()
-    out["summary"] = summary(out)  # last: inside the driver's tail of the line
-    print(json.dumps(out), flush=True)
-    plan.close()
-    if world > 1:
-        _lib.comm_destroy()
-    group.close()
 
 
 if __name__ == "__main__":

@@ -6,7 +6,8 @@ Run in the build container only (the reference is not present on the GPU box):
 
 It imports pranislav/Spatial_Light_Modulator_Module's src/algorithms.py from the
 given directory, runs gerchberg_saxton / gradient_descent / make_initial_guess
-on seeded inputs and stores inputs and outputs as .npz data files. Nothing from
+on seeded inputs and stores inputs and outputs as .npz data files (a set too
+large for one file continues in <name>.partN.npz, oracle/goldens.py). Nothing from
 the reference's source is copied into the repository: only the numbers.
 """
 from __future__ import annotations
@@ -22,6 +23,9 @@ import sys
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+
+from oracle import goldens  # noqa: E402  (a set over the per-file size limit is stored in parts)
 
 
 def ns(**kw):
@@ -72,16 +76,16 @@ def main():
     ):
         phi30, _, err30 = quiet(alg.gerchberg_saxton, target, ns(max_loops=30))
         phi230, exp230, err230 = quiet(alg.gerchberg_saxton, target, ns(max_loops=230))
-        np.savez_compressed(os.path.join(HERE, tag + ".npz"), target=target, phi30=phi30, phi230=phi230,
-                            expected230=exp230.astype(np.float32), err230=np.array(err230),
-                            err30=np.array(err30))
+        goldens.save(os.path.join(HERE, tag + ".npz"), target=target, phi30=phi30, phi230=phi230,
+                     expected230=exp230.astype(np.float32), err230=np.array(err230),
+                     err30=np.array(err30))
         print(tag, "final error", err230[-1])
 
     # G3: sparse trap target, cold start, full outputs (faithful-oracle check)
     t3 = trap_target(128, 3)
     phi, exp3, err3 = quiet(alg.gerchberg_saxton, t3, ns(max_loops=20))
-    np.savez_compressed(os.path.join(HERE, "g3_gs_traps_128.npz"), target=t3, phi=phi, expected=exp3,
-                        err=np.array(err3))
+    goldens.save(os.path.join(HERE, "g3_gs_traps_128.npz"), target=t3, phi=phi, expected=exp3,
+                 err=np.array(err3))
 
     # G4 / G5: GD float32 256^2, seed 42, lr 0.005, wa 1 (config 3 recipe, smaller)
     t4 = np.random.default_rng(4242).uniform(0, 255, (256, 256)).astype(np.float32)
@@ -89,9 +93,9 @@ def main():
     phi4, out4, err4 = quiet(alg.gradient_descent, t4, a)
     a5 = ns(max_loops=500, initial_guess="random", random_seed=42)
     phi5, _, err5 = quiet(alg.gradient_descent, t4, a5)
-    np.savez_compressed(os.path.join(HERE, "g4_gd_f32_256.npz"), target=t4, phi100=phi4,
-                        output100=out4.astype(np.float32), err100=np.array(err4), phi500=phi5.astype(np.float32),
-                        err500=np.array(err5))
+    goldens.save(os.path.join(HERE, "g4_gd_f32_256.npz"), target=t4, phi100=phi4,
+                 output100=out4.astype(np.float32), err100=np.array(err4), phi500=phi5.astype(np.float32),
+                 err500=np.array(err5))
 
     # G6: dtype probes
     sq = np.sqrt(np.arange(256, dtype=np.uint8))
@@ -100,9 +104,9 @@ def main():
     guess = quiet(alg.make_initial_guess, "random", np.ones((16, 16)), np.zeros((16, 16)), 42)
     guesses = {k: quiet(alg.make_initial_guess, k, np.ones((8, 8)), np.zeros((8, 8)), 7)
                for k in ("old", "unnormed", "zeros", "ones")}
-    np.savez_compressed(os.path.join(HERE, "g6_probes.npz"), sqrt_u8=sq, sqrt_u8_dtype=str(sq.dtype),
-                        py_random_42=py_draws, guess_random_16=guess,
-                        **{f"guess_{k}_8": v for k, v in guesses.items()})
+    goldens.save(os.path.join(HERE, "g6_probes.npz"), sqrt_u8=sq, sqrt_u8_dtype=str(sq.dtype),
+                 py_random_42=py_draws, guess_random_16=guess,
+                 **{f"guess_{k}_8": v for k, v in guesses.items()})
 
     # G7: edge cases of the control flow
     edges = {}
@@ -122,9 +126,9 @@ def main():
     quiet(alg.gradient_descent, t3.astype(np.float32)[:64, :64], a7)
     a8 = ns(max_loops=60, tolerance=1e9)
     _, _, err_tol = quiet(alg.gerchberg_saxton, t3, a8)
-    np.savez_compressed(os.path.join(HERE, "g7_edges.npz"), gs_zero_loops=edges["gs_zero_loops"],
-                        gd_bad_guess=edges["gd_bad_guess"], zeros_target_err=np.array(errz),
-                        unsettle_lr_after=a7.learning_rate, tol_hit_err=np.array(err_tol))
+    goldens.save(os.path.join(HERE, "g7_edges.npz"), gs_zero_loops=edges["gs_zero_loops"],
+                 gd_bad_guess=edges["gd_bad_guess"], zeros_target_err=np.array(errz),
+                 unsettle_lr_after=a7.learning_rate, tol_hit_err=np.array(err_tol))
 
     # G8: non-uniform incoming intensity read from a PNG path (src/algorithms.py:14-19)
     png = os.path.join(HERE, "g8_incoming_128.png")
@@ -133,15 +137,15 @@ def main():
     a_rel = os.path.relpath(png)
     phi8a, _, _ = quiet(alg.gerchberg_saxton, t8, ns(max_loops=10, incomming_intensity=png))
     phi8b, exp8, err8 = quiet(alg.gerchberg_saxton, t8, ns(max_loops=40, incomming_intensity=png))
-    np.savez_compressed(os.path.join(HERE, "g8_gs_ain_128.npz"), target=t8, phi10=phi8a, phi40=phi8b,
-                        expected40=exp8.astype(np.float32), err40=np.array(err8), png=a_rel)
+    goldens.save(os.path.join(HERE, "g8_gs_ain_128.npz"), target=t8, phi10=phi8a, phi40=phi8b,
+                 expected40=exp8.astype(np.float32), err40=np.array(err8), png=a_rel)
 
     # G9: GD, "fourier" initial guess, white_attention 2, unsettle 1, uint8 target
     t9 = trap_target(128, 9, count=30, radius=3)
     a9 = ns(max_loops=60, initial_guess="fourier", white_attention=2.0, unsettle=1, learning_rate=0.002)
     phi9, out9, err9 = quiet(alg.gradient_descent, t9, a9)
-    np.savez_compressed(os.path.join(HERE, "g9_gd_fourier_u8_128.npz"), target=t9, phi=phi9,
-                        output=out9.astype(np.float32), err=np.array(err9), lr_after=a9.learning_rate)
+    goldens.save(os.path.join(HERE, "g9_gd_fourier_u8_128.npz"), target=t9, phi=phi9,
+                 output=out9.astype(np.float32), err=np.array(err9), lr_after=a9.learning_rate)
     print("done")
 
 

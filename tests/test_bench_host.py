@@ -48,6 +48,7 @@ class _FakePlan:
         return (st, np.full(total, -1, np.int32)) if want else (None, None)
 
     def run_timed(self, loops, **k):
+        assert not os.environ.get("BENCH_TEST_PLAIN"), "a plain run timed a run of its own"
         us = np.array([8.0 * loops, 7.5 * (loops - 1), 0.0, 30.0])
         cnt = np.array([loops, loops - 1, 0, 7], np.int32)
         return us, cnt
@@ -65,6 +66,7 @@ class _FakePlan:
         return self.rank
 
     def time_gather(self, counts, root=0, reps=5):
+        assert not os.environ.get("BENCH_TEST_PLAIN"), "a plain run timed the gather on its own"
         return 0.25, 0 if self.rank == root else self.batch * self.height * self.width * 4
 
     def close(self):
@@ -115,17 +117,19 @@ def _fake_lib(rank, fail_init=False):
     return Fake
 
 
-def _rank(rank, world, port, out, fail_rank=-1):
+def _rank(rank, world, port, out, fail_rank=-1, full=True):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port), SLM_RDZV_PORT=str(port), SLM_JOB_TOKEN="bench-host-test")
     if fail_rank >= 0:
         os.environ["BENCH_TEST_NO_COMM"] = "1"
+    if not full:
+        os.environ["BENCH_TEST_PLAIN"] = "1"
     sys.path.insert(0, ROOT)
     import bench
 
     bench._lib = _fake_lib(rank, fail_init=rank == fail_rank)
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--size", "64", "--iters", "10",
-                "--batch-per-gpu", "2"]
+                "--batch-per-gpu", "2"] + (["--full"] if full else ["--dump-outputs", out + ".d"])
     with open(out, "w") as f:
         sys.stdout = f
         bench.main()
@@ -164,6 +168,31 @@ def test_bench_two_ranks_json_shape(tmp_path):
         assert "plan stream" in d["gather_stream"] or "overlaps the next run" in d["gather_stream"]
 
 
+def test_bench_two_ranks_plain_run_prints_the_headline_only(tmp_path):
+    """Without --full the ranks time their steps and rank 0 prints the headline
+    fields: no run or gather timed on its own, no per-rank records; with
+    --dump-outputs rank 0 alone writes every rank's holograms."""
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    procs = [ctx.Process(target=_rank, args=(r, 2, port, str(tmp_path / f"r{r}.out"), -1, False)) for r in range(2)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(120)
+        assert p.exitcode == 0
+    lines = [ln for ln in (tmp_path / "r0.out").read_text().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and not (tmp_path / "r1.out").read_text().strip()
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1 and out["config"]["global_batch"] == 4
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["dtype"] == "f32" and out["higher_is_better"] is True
+    assert not {"roofline", "check", "ranks", "extra", "cpu_baseline", "summary"} & set(out)
+    assert np.load(tmp_path / "r0.out.d" / "phase.npy").shape == (4, 64, 64)
+    assert np.load(tmp_path / "r0.out.d" / "error.npy").shape == (4, 10)
+    assert not (tmp_path / "r1.out.d").exists()
+
+
 def test_bench_rank_without_device_stops_every_rank(tmp_path):
     """A rank whose GPU fails to initialise makes every rank exit with an error
     before any of them enters RCCL's communicator set-up (where the others
@@ -179,6 +208,27 @@ def test_bench_rank_without_device_stops_every_rank(tmp_path):
         p.join(120)
         assert p.exitcode == 1
     assert not [ln for ln in (tmp_path / "r0.out").read_text().splitlines() if ln.startswith("{")]
+
+
+def test_dump_outputs_samples_large_arrays_the_same_way_every_time(tmp_path, monkeypatch):
+    """--dump-outputs keeps an array within its share of the byte budget whole
+    and cuts a larger one to a fixed seeded sample of its elements, identical
+    from call to call, so two builds' dumps line up element for element."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert bench.DUMP_BUDGET <= 64_000_000
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 8000)
+    big = np.arange(5000, dtype=np.float32).reshape(5, 10, 100)
+    small = np.linspace(0, 1, 40).reshape(5, 8)
+    a = bench.dump_outputs(str(tmp_path / "a"), {"phase": big, "error": small})
+    b = bench.dump_outputs(str(tmp_path / "b"), {"phase": big + 1, "error": small})
+    assert a == b == {"phase": {"shape": [1000], "dtype": "float32"}, "error": {"shape": [5, 8], "dtype": "float64"}}
+    pa, pb = np.load(tmp_path / "a" / "phase.npy"), np.load(tmp_path / "b" / "phase.npy")
+    assert pa.dtype == np.float32 and (np.diff(pa) >= 0).all() and len(np.unique(pa)) > 800
+    np.testing.assert_array_equal(pb, pa + 1)  # the same elements of both arrays
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "error.npy"), small)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 8000 + 2 * 128
 
 
 def test_cpu_baseline_configs0_times_whole_runs():

@@ -11,11 +11,12 @@ import os
 import numpy as np
 import pytest
 
+from oracle import goldens
 from oracle import gs_gd_oracle as orc
 
 
 def golden(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name), allow_pickle=False)
+    return goldens.load(os.path.join(golden_dir, name))
 
 
 def gd_args(**kw):

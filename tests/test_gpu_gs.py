@@ -12,13 +12,14 @@ import os
 import numpy as np
 import pytest
 
+from oracle import goldens
 from oracle import gs_gd_oracle as orc
 
 PHASE_RMS_TOL = 1e-5  # north_star: <= 1e-5 rms on the output phase (float32)
 
 
 def golden(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name), allow_pickle=False)
+    return goldens.load(os.path.join(golden_dir, name))
 
 
 def args_ns(**kw):

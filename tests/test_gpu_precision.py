@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import scipy.fft as sfft
 
+from oracle import goldens
 from oracle import gs_gd_oracle as orc
 
 PHASE_RMS_TOL = 1e-5
@@ -43,7 +44,7 @@ def _gpu_warm_run(lib, t, phi_w, span, precision):
 @pytest.mark.parametrize("name", ["g1_gs_u8_256.npz", "g2_gs_f32_256.npz"])
 @pytest.mark.parametrize("prec", ["f32", "f64"])
 def test_reference_goldens_both_precisions(gpu, golden_dir, name, prec):
-    g = np.load(os.path.join(golden_dir, name), allow_pickle=False)
+    g = goldens.load(os.path.join(golden_dir, name))
     precision = gpu.PRECISION_F32 if prec == "f32" else gpu.PRECISION_F64
     ph, err = _gpu_warm_run(gpu, g["target"], g["phi30"], 200, precision)
     rms = orc.phase_rms(ph, g["phi230"])

@@ -16,6 +16,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from oracle import goldens
 from oracle import gs_gd_oracle as orc
 
 
@@ -176,7 +177,7 @@ def test_one_shot_entry_points_as_integration_binds_them(gpu, golden_dir):
     from spatial_light_modulator_module_amd import algorithms as alg
 
     gs_hip, gd_hip = _integration_binding(_lib.LIB_PATH)
-    g = np.load(f"{golden_dir}/g1_gs_u8_256.npz", allow_pickle=False)
+    g = goldens.load(f"{golden_dir}/g1_gs_u8_256.npz")
     t = g["target"]
     # cold start: chaotic at rounding level, so the first errors are
     # compared with the reference and the rest with the plan API bit for bit
@@ -186,7 +187,7 @@ def test_one_shot_entry_points_as_integration_binds_them(gpu, golden_dir):
     np.testing.assert_array_equal(phase, ph_p[0].astype(np.float64))
     np.testing.assert_array_equal(expected, e_p[0])
     assert err == err_p[0]
-    g4 = np.load(f"{golden_dir}/g4_gd_f32_256.npz", allow_pickle=False)
+    g4 = goldens.load(f"{golden_dir}/g4_gd_f32_256.npz")
     t4 = g4["target"]
     x0 = alg.make_initial_guess("random", None, t4, 42)
     ph, _, err = gd_hip(t4, 100, np.full(100, 0.005), 1.0, x0)

@@ -10,11 +10,12 @@ import os
 import numpy as np
 import pytest
 
+from oracle import goldens
 from oracle import gs_gd_oracle as orc
 
 
 def load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name), allow_pickle=False)
+    return goldens.load(os.path.join(golden_dir, name))
 
 
 @pytest.mark.parametrize("name", ["g1_gs_u8_256.npz", "g2_gs_f32_256.npz"])

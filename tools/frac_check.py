@@ -4,6 +4,9 @@ of the same bench command, and record the result in profiles/rocprof_kernels.jso
 
     python tools/frac_check.py <kernel_trace.csv> <bench.json (un-profiled run)> [--source NAME] [--write]
 
+Both runs are `bench.py --full` (the roofline object and the event-timed run
+are part of a --full run only).
+
 For the dominant GS kernels of the bench configuration (col_main =
 col_kernel<col_plan, cw, GS_MAIN, ...>, row_main = row_kernel<row_plan,
 GS_MAIN, ...>) it prints the trace's mean duration over every launch (graph

@@ -15,10 +15,10 @@ if [ "$2" != "skip-tests" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { echo "smoke failed rc=$?"; tail -30 $out/smoke.log; exit 1; }
   tail -3 $out/smoke.log
 fi
-timeout -k 10 600 python bench.py > $out/bench.json 2> $out/bench.err || { echo "bench failed rc=$?"; tail -30 $out/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $out/bench.json 2> $out/bench.err || { echo "bench failed rc=$?"; tail -30 $out/bench.err; exit 1; }
 cat $out/bench.json
 cd /tmp && export TMPDIR=/tmp && cd $repo
-B="bench.py --steps 5 --warmup 1 --no-extra --no-cpu-baseline"
+B="bench.py --steps 5 --warmup 1 --full --no-extra --no-cpu-baseline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o trace -- python3 $B > $out/trace.log 2>&1 || { echo "trace failed rc=$?"; tail -20 $out/trace.log; exit 1; }
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch -o fetch -- python3 $B > $out/fetch.log 2>&1 || { echo "fetch pass failed rc=$?"; tail -20 $out/fetch.log; exit 1; }
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write -o write -- python3 $B > $out/write.log 2>&1 || { echo "write pass failed rc=$?"; tail -20 $out/write.log; exit 1; }
