@@ -213,6 +213,52 @@ def gerchberg_saxton_c64(demanded_output, loops, incoming_intensity=None, initia
     return np.angle(a).astype(np.float32), e, np.array(stats)
 
 
+def gradient_descent_c64(demanded_output, loops, learning_rates, white_attention=1.0, initial_field=None,
+                         incoming_intensity=None):
+    """GD (src/algorithms.py:60-112) with the GPU's number formats: complex64
+    state, float32 element-wise arithmetic, pocketfft on complex64 input
+    (single precision). Same arguments and loop as
+    oracle.fast_f64.gradient_descent_f64, no tolerance stop. Its distance to
+    the float64 loop is what float32 rounding of every stage costs, in another
+    butterfly order than the kernels': the yardstick for per-pixel bounds.
+    Returns (angle(x) float32, output float32, error_evolution, x complex64)."""
+    t = np.asarray(demanded_output)
+    h, w = t.shape
+    tf = t.astype(np.float32)
+    t64 = t.astype(np.float64)
+    one = np.float32(1)
+    a_in = one
+    if incoming_intensity is not None:
+        a_in = np.sqrt(np.asarray(incoming_intensity, np.float64)).astype(np.float32)
+    norm = np.float32(np.amax(t))
+    mask = one + np.float32(white_attention) * tf / np.float32(255)
+    x = np.array(initial_field).astype(np.complex64)
+    rates = np.broadcast_to(np.asarray(learning_rates, np.float32), (loops,))
+    out = None
+    err_evol = []
+    for i in range(loops):
+        u = (x / np.abs(x) * a_in).astype(np.complex64)
+        f = sfft.fft2(u)
+        out = f.real * f.real + f.imag * f.imag
+        out = out * (norm / out.max())
+        err_evol.append(np.float64(np.sum((out.astype(np.float64) - t64) ** 2) / (h * w)))
+        g = sfft.ifft2(f * (mask * (out - tf))) * a_in
+        ax2 = x.real * x.real + x.imag * x.imag
+        re = x.real * g.real + x.imag * g.imag
+        x = x - rates[i] * ((g - x * (re / ax2)) / np.sqrt(ax2))
+        assert f.dtype == g.dtype == x.dtype == np.complex64 and out.dtype == np.float32
+    return np.angle(x), out, err_evol, x
+
+
+def fourier_guess_c64(demanded_output, incoming_intensity=None):
+    """The "fourier" guess a_in exp(i angle(ifft2(sqrt T))) (src/algorithms.py:
+    153-155) in complex64 / float32, with z/|z| for exp(i angle(z))."""
+    a_t = np.sqrt(np.asarray(demanded_output).astype(np.float32))
+    a_in = np.float32(1) if incoming_intensity is None else np.sqrt(
+        np.asarray(incoming_intensity, np.float64)).astype(np.float32)
+    return _unit(sfft.ifft2(a_t.astype(np.complex64)), a_in)
+
+
 def error_from_stats(stats, norm, sum_t2, space_norm):
     """error_f of E * norm / max(E) expanded in the accumulated sums, evaluated
     in the same operation order as the device (kernels.hpp reduce_slab)."""
