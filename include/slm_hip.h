@@ -135,6 +135,19 @@ long long slm_plan_kernel_bytes(slm_plan* plan, int kernel_class);
  * info[5] / info[6] = radix plan keys of rows / columns, info[7] = precision
  * (info must hold 8 ints) */
 int slm_plan_info(slm_plan* plan, int* info);
+/* The geometry an any-size plan (engines 2 .. 5 of slm_plan_engine) runs, as
+ * chosen at its creation from the shape, the batch, the device and the
+ * $SLM_GENERIC_ENGINE / $SLM_RZ_* / $SLM_MR_* overrides (info must hold 8 ints):
+ * info[0] = engine (slm_plan_engine's code), info[1] = precision,
+ * info[2] / info[3] = radix plan keys of rows / columns (-1 off the radix-plan
+ * engines 4 and 5), info[4] = rows per row tile, info[5] = columns per column
+ * tile, info[6] = state layout between the passes (0 = row-major, 1 = two-
+ * column panels; always 0 off engines 4 and 5), info[7] = column workgroups
+ * per hologram. Engine 2 (line transforms) has no tiles: info[4] = info[5] = 1,
+ * info[7] = 0. A plan of the fused float32 engine is refused with
+ * SLM_ERR_STATE and info is left untouched: slm_plan_info describes those
+ * (and keeps reporting 0 / 1 / -1 for any-size plans). */
+int slm_plan_generic_info(slm_plan* plan, int* info);
 /* panel widths (log2) of the plan's two blocked device layouts: X (row-pass
  * output, column-pass input, target) and Y (column-pass output, GD field) */
 int slm_plan_layout(slm_plan* plan, int* x_log2, int* y_log2);
@@ -188,8 +201,11 @@ int slm_gs_multi_timing(int max_shards, double* wall_ms, double* run_ms);
 /* unscaled 2-D C2C transform of [batch][h][w] complex64 (test entry) */
 int slm_fft2(const float* in_re_im, float* out_re_im, int batch, int height, int width, int inverse);
 /* unscaled 2-D C2C transform of [batch][h][w] complex128 in float64 arithmetic
- * (any shape: mixed-radix kernels where both sides factor into 2..13, else
- * chirp-z line transforms) -> the float64 scipy.fft.ifft2 of move_traps.update_hologram,
+ * (any shape with sides up to 4096, or up to 8192 without a prime factor
+ * above 13: mixed-radix kernels where both sides factor into 2..13, else
+ * chirp-z line transforms; the engines are cached per (device, batch, h, w)
+ * and the $SLM_ENGINE / $SLM_GENERIC_ENGINE / $SLM_RZ_* / $SLM_MR_* overrides
+ * in force) -> the float64 scipy.fft.ifft2 of move_traps.update_hologram,
  * src/move_traps.py:66 (times h w) */
 int slm_fft2_c128(const double* in_re_im, double* out_re_im, int batch, int height, int width, int inverse);
 /* frees the float64 engines slm_fft2_c128 keeps per (device, batch, h, w)

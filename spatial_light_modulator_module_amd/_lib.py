@@ -78,6 +78,7 @@ _SIGNATURES = [
     ("slm_plan_read_field", _c_int, [_vp, _vp]),
     ("slm_plan_kernel_bytes", ctypes.c_longlong, [_vp, _c_int]),
     ("slm_plan_info", _c_int, [_vp, _vp]),
+    ("slm_plan_generic_info", _c_int, [_vp, _vp]),
     ("slm_plan_layout", _c_int, [_vp, _vp, _vp]),
     ("slm_plan_engine", _c_int, [_vp, _vp, _vp]),
     ("slm_plan_device", _c_int, [_vp]),
@@ -329,6 +330,20 @@ class Plan:
                 "col_plan": int(a[6]), "precision": "f64" if a[7] == PRECISION_F64 else "f32",
                 "layout": self.layout(), "engine": self.engine()}
 
+    def generic_info(self) -> dict:
+        """The geometry an any-size plan runs (slm_plan_generic_info): engine
+        name, precision, radix plan keys of rows / columns (-1 off the
+        radix-plan engines), rows per row tile, columns per column tile, state
+        layout ("rm" row-major, "b2" two-column panels) and column workgroups
+        per hologram. Raises SlmError for a plan of the fused float32 engine
+        (info() describes those)."""
+        a = np.zeros(8, np.int32)
+        check(self._lib.slm_plan_generic_info(self.handle, ptr(a)), "slm_plan_generic_info")
+        names = ("stockham", "shuffle", "bluestein", "mixed-radix", "radix-c128", "radix-c64")
+        return {"engine": names[int(a[0])], "precision": "f64" if a[1] == PRECISION_F64 else "f32",
+                "row_plan": int(a[2]), "col_plan": int(a[3]), "rows_per_tile": int(a[4]),
+                "cols_per_tile": int(a[5]), "layout": "b2" if a[6] else "rm", "col_workgroups": int(a[7])}
+
     @property
     def device(self) -> int:
         """HIP device of the plan (slm_plan_device)."""
@@ -410,7 +425,8 @@ def fft2(x: np.ndarray, inverse: bool = False) -> np.ndarray:
 
 def fft2_c128(x: np.ndarray, inverse: bool = False) -> np.ndarray:
     """Unscaled 2-D C2C transform of [..., H, W] complex128 in float64 on the
-    GPU (slm_fft2_c128: the any-size engine's transforms, any shape)."""
+    GPU (slm_fft2_c128: the any-size engine's transforms; sides up to 4096, or
+    up to 8192 without a prime factor above 13)."""
     init()
     a = np.ascontiguousarray(x, dtype=np.complex128)
     shape = a.shape

@@ -53,17 +53,37 @@ from ._lib import ALGO_GD, ALGO_GS, TGT_F32, TGT_U8
 # ---------------------------------------------------------------------------
 
 
+def _side_supported(n: int) -> bool:
+    """One line is one workgroup's LDS (8192 complex128): a 13-smooth side up
+    to 8192 transforms directly, any other side by chirp-z over a length
+    >= 2n - 1, so up to 4096."""
+    if n <= 4096:
+        return True
+    if n > 8192:
+        return False
+    for p in (2, 3, 5, 7, 11, 13):
+        while n % p == 0:
+            n //= p
+    return n == 1
+
+
 def _check_shape(t: np.ndarray):
-    """Any (h, w), as the reference (src/algorithms.py:20-27): sides in
-    SUPPORTED_LENGTHS run the fused FFT kernels, every other shape the
-    float64 any-size engine (csrc/generic.hip: mixed-radix kernels for
-    13-smooth sides, chirp-z line transforms otherwise)."""
+    """(h, w) with every side up to 4096, or up to 8192 where the side has no
+    prime factor above 13 (the reference takes any shape,
+    src/algorithms.py:20-27): sides in SUPPORTED_LENGTHS run the fused FFT
+    kernels, every other shape the float64 any-size engine (csrc/generic.hip:
+    mixed-radix kernels for 13-smooth sides, chirp-z line transforms
+    otherwise, whose line must fit one workgroup's LDS)."""
     if t.ndim != 2:
         # the reference unpacks `w, l = demanded_output.shape` (src/algorithms.py:20)
         raise ValueError(f"too many values to unpack (expected 2): target has shape {t.shape}")
     h, w = t.shape
     if h < 1 or w < 1:
         raise ValueError(f"empty target of shape {t.shape}")
+    for n in (h, w):
+        if not _side_supported(n):
+            raise ValueError(f"unsupported target shape {t.shape}: a side over 4096 with a prime factor above 13, "
+                             f"or any side over 8192, does not fit the GPU transforms (side {n})")
     return h, w
 
 

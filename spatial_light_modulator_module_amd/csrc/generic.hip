@@ -577,7 +577,9 @@ int line_plan(GenericEngine* g, int n, bool chirp_z, mr::LineArgs* la, bool* big
     };
     while (!smooth5(M)) ++M;
     if (M > mr::kMaxLine)
-        return slm_set_error(SLM_ERR_UNSUPPORTED, "line transforms: side too long for one workgroup's chirp-z line");
+        return slm_set_error(SLM_ERR_UNSUPPORTED,
+                             "unsupported side: a side over 4096 with a prime factor above 13, or any side over "
+                             "8192, does not fit one workgroup's chirp-z line (8192 points)");
     std::vector<int> rev;
     if (int rc = mr_plan_line(g, M, &la->pl, st, &rev)) return rc;
     la->direct = 0;
@@ -971,6 +973,17 @@ bool generic_uses_blas(const GenericEngine* g) {
 
 int generic_kind(const GenericEngine* g) {  // 2: line transforms
     return !g ? -1 : g->rz ? (g->prec == PREC_F32 ? 5 : 4) : g->mr ? 3 : 2;
+}
+
+void generic_info(const GenericEngine* g, int info[8]) {
+    info[0] = generic_kind(g);
+    info[1] = g->prec;
+    info[2] = g->rz ? g->rkey : -1;
+    info[3] = g->rz ? g->ckey : -1;
+    info[4] = g->mr ? g->rpw : 1;
+    info[5] = g->rz ? g->rz_cw : g->mr ? 1 << g->cw_log2 : 1;
+    info[6] = g->rz ? g->rz_lay : 0;
+    info[7] = g->mr ? g->nwg_col : 0;
 }
 
 void generic_destroy(GenericEngine* g) {

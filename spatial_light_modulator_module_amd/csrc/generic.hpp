@@ -53,6 +53,13 @@ bool generic_uses_blas(const GenericEngine* g);
 // back end: 2 line transforms (chirp-z), 3 mixed radix, 4 complex128 radix plans,
 // 5 complex64 radix plans (slm_plan_engine codes)
 int generic_kind(const GenericEngine* g);
+// the geometry the engine was created with (slm_plan_generic_info, slm_hip.h):
+// info[0] = generic_kind, [1] = precision, [2] / [3] = row / column plan key
+// (-1 off the radix-plan back ends), [4] = rows per row tile, [5] = columns
+// per column tile, [6] = state layout (radix_c128.hpp LAY_RM 0 / LAY_B2 1;
+// 0 = row-major off the radix-plan back ends), [7] = column workgroups per
+// hologram. The line-transform back end has no tiles: [4] = [5] = 1, [7] = 0.
+void generic_info(const GenericEngine* g, int info[8]);
 int generic_create(const GenericView& v, GenericEngine** out);
 void generic_destroy(GenericEngine* g);
 // one full run (setup, loops iterations, phase and expected output, statistics),

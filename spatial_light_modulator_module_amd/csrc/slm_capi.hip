@@ -1523,6 +1523,13 @@ int slm_plan_info(slm_plan* p, int* info) {
     return 0;
 }
 
+int slm_plan_generic_info(slm_plan* p, int* info) {
+    if (!p || !info) return fail(SLM_ERR_ARG, "null argument");
+    if (!p->gen) return fail(SLM_ERR_STATE, "not an any-size plan (fused float32 engine: see slm_plan_info)");
+    generic_info(p->gen, info);
+    return 0;
+}
+
 int slm_plan_engine(slm_plan* p, int* col_engine, int* row_engine) {
     if (!p || !col_engine || !row_engine) return fail(SLM_ERR_ARG, "null argument");
     // mirrors kernels.hpp: kShuffle<K, P> && (CW == 2 | RPW == 2) && one line per thread
@@ -1713,9 +1720,12 @@ namespace {
 // drop-in's plans: move_traps.update_hologram calls it for every non-blank
 // image of the interactive trap loop, which rebuilt stream, buffers, line
 // plans and tables each time before r06. A few shapes are kept (oldest out);
-// slm_release_caches frees them (algorithms.clear_plans).
+// slm_release_caches frees them (algorithms.clear_plans). generic_create reads
+// the engine and geometry overrides from the environment, so an entry also
+// keeps their values at its creation: a call under other values builds its own.
 struct C128Entry {
     int device = 0, batch = 0, h = 0, w = 0;
+    std::string knobs;
     slm_plan* q = nullptr;  // scratch GS view: its stream and engine only
     double2* buf = nullptr;
 };
@@ -1730,9 +1740,22 @@ void c128_free(C128Entry& e) {
     e.q = nullptr;
 }
 
+// the environment generic_create's choices depend on (generic.hip)
+std::string c128_knobs() {
+    std::string s;
+    for (const char* name : {"SLM_ENGINE", "SLM_GENERIC_ENGINE", "SLM_RZ_PLAN", "SLM_RZ_ROW_PLAN", "SLM_RZ_COL_PLAN",
+                             "SLM_RZ_CW", "SLM_RZ_LAYOUT", "SLM_RZ_PANEL", "SLM_MR_RPW", "SLM_MR_CW"}) {
+        const char* v = std::getenv(name);
+        s += v ? v : "";
+        s += '\n';
+    }
+    return s;
+}
+
 int c128_entry(int batch, int height, int width, C128Entry** out) {
+    const std::string knobs = c128_knobs();
     for (auto& e : g_c128)
-        if (e.device == g_device && e.batch == batch && e.h == height && e.w == width) {
+        if (e.device == g_device && e.batch == batch && e.h == height && e.w == width && e.knobs == knobs) {
             *out = &e;
             return 0;
         }
@@ -1747,6 +1770,7 @@ int c128_entry(int batch, int height, int width, C128Entry** out) {
     e.batch = batch;
     e.h = height;
     e.w = width;
+    e.knobs = knobs;
     e.q = new slm_plan();
     slm_plan& q = *e.q;
     q.algo = SLM_ALGO_GS;

@@ -235,8 +235,11 @@ def test_generic_incoming_amplitude_gs_and_gd(gpu, engine):
                                    (49, 20), (121, 169)])
 def test_mixed_radix_fft2_c128_vs_numpy(gpu, shape):
     """slm_fft2_c128 (float64 in and out) on the mixed-radix kernels, every
-    radix and the ragged / degenerate tiles, against numpy.fft at float64
-    accuracy."""
+    radix and one-line sides, against numpy.fft at float64 accuracy, on the
+    tiles the heuristic picks (one row / one column at the small shapes; two
+    rows and two columns at 1080 x 1920, sixteen columns at 8 x 8192, which
+    divide evenly). Tail row tiles and ragged column tiles are forced in
+    test_gpu_tile_geometry.py."""
     rng = np.random.default_rng(2)
     x = rng.standard_normal((2,) + shape) + 1j * rng.standard_normal((2,) + shape)
     for inverse in (False, True):

@@ -129,12 +129,24 @@ def test_gd_argument_errors():
 
 
 def test_shape_checks():
-    """Any (h, w) is accepted, as the reference's (src/algorithms.py:20-27);
-    only a non-2-D target fails the reference's own unpacking."""
+    """Shapes without a radix plan are accepted, as the reference's
+    (src/algorithms.py:20-27), up to the line transforms' limit
+    (test_shape_limit_of_the_line_transforms); a non-2-D target fails the
+    reference's own unpacking."""
     assert alg._check_shape(np.ones((100, 64))) == (100, 64)
     assert alg._check_shape(np.ones((1, 3))) == (1, 3)
     with pytest.raises(ValueError):
         alg.gerchberg_saxton(np.ones((4, 100, 64)), _args())
+
+
+def test_shape_limit_of_the_line_transforms():
+    """A line is one workgroup's LDS: 13-smooth sides up to 8192 transform
+    directly, other sides by chirp-z over >= 2n - 1 points, so up to 4096."""
+    for shape in [(4096, 4093), (8192, 2), (7168, 6561), (2, 4095)]:
+        assert alg._check_shape(np.ones(shape, np.uint8)) == shape
+    for shape in [(4099, 2), (2, 8200), (4097, 64), (8193, 8), (64, 5000 * 2 + 2)]:
+        with pytest.raises(ValueError, match="over 4096 with a prime factor above 13, or any side over 8192"):
+            alg._check_shape(np.ones(shape, np.uint8))
 
 
 @pytest.mark.parametrize("loops,unsettle", [(10, 0), (10, 1), (12, 3), (7, 2), (100, 4)])
