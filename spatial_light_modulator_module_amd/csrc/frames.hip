@@ -31,7 +31,7 @@
 #include <cstdint>
 #include <mutex>
 
-#include "../../include/slm_hip.h"
+#include "runtime.hpp"
 
 namespace {
 
@@ -160,26 +160,25 @@ int grid_for(long long n) { return (int)std::min<long long>(8192, (n + 255) / 25
 
 }  // namespace
 
-// shared with slm_capi.hip: error text for slm_last_error(), device selection
-int slm_set_error(int code, const char* msg);
-int slm_current_device_ready();
+using slm::fail;
 
-#define FR_TRY(expr)                                                    \
-    do {                                                                \
-        hipError_t e_ = (expr);                                         \
-        if (e_ != hipSuccess) return slm_set_error(SLM_ERR_HIP, #expr); \
+// the error text is the failed expression alone
+#define FR_TRY(expr)                                                  \
+    do {                                                              \
+        hipError_t e_ = (expr);                                       \
+        if (e_ != hipSuccess) return fail(SLM_ERR_HIP, "%s", #expr);  \
     } while (0)
 
 extern "C" {
 
 int slm_trap_frames(int batch, int height, int width, const int* ys, const int* xs, const double* mask,
                     double ct2pi, int rule, double* phase_out, unsigned char* frame_out) {
-    if (batch < 1 || height < 1 || width < 1 || !ys || !xs) return slm_set_error(SLM_ERR_ARG, "bad trap arguments");
-    if (rule != SLM_QUANT_ASTYPE && rule != SLM_QUANT_PIL) return slm_set_error(SLM_ERR_ARG, "unknown rule");
+    if (batch < 1 || height < 1 || width < 1 || !ys || !xs) return fail(SLM_ERR_ARG, "bad trap arguments");
+    if (rule != SLM_QUANT_ASTYPE && rule != SLM_QUANT_PIL) return fail(SLM_ERR_ARG, "unknown rule");
     for (int b = 0; b < batch; ++b)
         if (ys[b] < 0 || ys[b] >= height || xs[b] < 0 || xs[b] >= width)
-            return slm_set_error(SLM_ERR_ARG, "trap coordinate outside the image");
-    if (int rc = slm_current_device_ready()) return rc;
+            return fail(SLM_ERR_ARG, "trap coordinate outside the image");
+    RC(slm::ensure_device());
     std::lock_guard<std::mutex> lk(g_frames_mu);
     if (!g_frames_stream) FR_TRY(hipStreamCreateWithFlags(&g_frames_stream, hipStreamNonBlocking));
     const long long holo = (long long)height * width, n = holo * batch;
@@ -221,11 +220,11 @@ int slm_trap_frames(int batch, int height, int width, const int* ys, const int* 
 
 int slm_quantize(const void* src, int src_type, const double* mask, int batch, int height, int width, double ct2pi,
                  int rule, unsigned char* out) {
-    if (!src || !out || batch < 1 || height < 1 || width < 1) return slm_set_error(SLM_ERR_ARG, "bad arguments");
-    if (src_type != SLM_SRC_F64 && src_type != SLM_SRC_I16) return slm_set_error(SLM_ERR_ARG, "unknown source");
+    if (!src || !out || batch < 1 || height < 1 || width < 1) return fail(SLM_ERR_ARG, "bad arguments");
+    if (src_type != SLM_SRC_F64 && src_type != SLM_SRC_I16) return fail(SLM_ERR_ARG, "unknown source");
     if (src_type == SLM_SRC_F64 && rule != SLM_QUANT_ASTYPE && rule != SLM_QUANT_PIL)
-        return slm_set_error(SLM_ERR_ARG, "unknown rule");
-    if (int rc = slm_current_device_ready()) return rc;
+        return fail(SLM_ERR_ARG, "unknown rule");
+    RC(slm::ensure_device());
     std::lock_guard<std::mutex> lk(g_frames_mu);
     if (!g_frames_stream) FR_TRY(hipStreamCreateWithFlags(&g_frames_stream, hipStreamNonBlocking));
     const long long holo = (long long)height * width, n = holo * batch;
@@ -254,9 +253,9 @@ int slm_quantize(const void* src, int src_type, const double* mask, int batch, i
 
 int slm_transform_hologram(const double* holo_in, int height, int width, int flags, const double* params,
                            double* holo_out) {
-    if (!holo_out || !params || height < 1 || width < 1) return slm_set_error(SLM_ERR_ARG, "bad arguments");
-    if (flags & ~(SLM_TRANSFORM_DEFLECT | SLM_TRANSFORM_LENS)) return slm_set_error(SLM_ERR_ARG, "unknown flags");
-    if (int rc = slm_current_device_ready()) return rc;
+    if (!holo_out || !params || height < 1 || width < 1) return fail(SLM_ERR_ARG, "bad arguments");
+    if (flags & ~(SLM_TRANSFORM_DEFLECT | SLM_TRANSFORM_LENS)) return fail(SLM_ERR_ARG, "unknown flags");
+    RC(slm::ensure_device());
     std::lock_guard<std::mutex> lk(g_frames_mu);
     if (!g_frames_stream) FR_TRY(hipStreamCreateWithFlags(&g_frames_stream, hipStreamNonBlocking));
     const long long n = (long long)height * width;

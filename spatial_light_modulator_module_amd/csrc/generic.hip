@@ -40,11 +40,32 @@
 #include "mixed_radix.hpp"
 #include "radix_c128.hpp"
 
-int slm_set_error(int code, const char* msg);  // slm_capi.hip
-
 namespace slm {
 
-struct GenericEngine {
+struct GenericEngine : Engine {
+    ~GenericEngine() override;
+    void* target_stage(const PlanState& v) override { return v.tgt; }  // kept row-major as uploaded
+    int land_target(PlanState&, const void*) override { return 0; }
+    int land_field(PlanState& v, const float* field) override;
+    int enqueue(PlanState& v, int loops, double tol, int checked, float wa, bool phase_set, bool field_set) override;
+    int set_precision(PlanState&, int) override { return fail(SLM_ERR_STATE, "any-size engines are rebuilt"); }
+    int read_field(PlanState& v, bool fresh, float* field) override;
+    int fft2(PlanState& v, const float* in, float* out, int inverse) override;
+    int fft2_z(PlanState& v, const double2* in, double2* out, int inverse) override;
+    int intensity(PlanState& v) override;
+    long long kernel_bytes(const PlanState& v, int cls) const override;
+    int kind() const { return rz ? (prec == PREC_F32 ? 5 : 4) : mr ? 3 : 2; }  // 2: line transforms
+    void codes(const PlanState&, int* col_engine, int* row_engine) const override { *col_engine = *row_engine = kind(); }
+    void layout(int* x_log2, int* y_log2) const override { *x_log2 = *y_log2 = 0; }  // row-major
+    void info(const PlanState& v, int info[8]) const override {
+        const int i[8] = {0, v.nwg, 0, 0, 1, -1, -1, v.prec};  // no fused-engine tiles or plan keys
+        std::copy(i, i + 8, info);
+    }
+    int generic_info(int info[8]) const override;
+    // device complex64 [B][H][W] transforms and the GD field (in may equal out)
+    int fft2_c64(const PlanState& v, const float2* in, float2* out, int inverse);
+    int field_c64(const PlanState& v, float2* out);
+
     // mixed-radix back end: line plans (twiddles, digit reversal) of both sides
     bool mr = false;
     // complex128 radix-plan back end (mr is set too: same launch structure and
@@ -78,10 +99,11 @@ namespace {
 
 constexpr int kGT = 256;  // threads per block of the element-wise kernels
 
-#define G_HIP(expr)                                                                      \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess) return slm_set_error(SLM_ERR_HIP, hipGetErrorString(e_));  \
+// the error text is HIP's message alone
+#define G_HIP(expr)                                                                   \
+    do {                                                                              \
+        hipError_t e_ = (expr);                                                       \
+        if (e_ != hipSuccess) return fail(SLM_ERR_HIP, "%s", hipGetErrorString(e_));  \
     } while (0)
 
 int grid_of(long long n) { return (int)std::min<long long>(16384, (n + kGT - 1) / kGT); }
@@ -357,19 +379,19 @@ __global__ void __launch_bounds__(256) k_transpose(const double2* in, double2* o
 // 1-D transforms of `lines` rows of the line plan's length
 int line_pass(const GenericEngine* g, const mr::LineArgs& base, bool big, const double2* in, double2* out,
               long long lines, bool inverse, hipStream_t st) {
-    if (lines > 0x7fffffffLL) return slm_set_error(SLM_ERR_UNSUPPORTED, "line transforms: too many lines");
+    if (lines > 0x7fffffffLL) return fail(SLM_ERR_UNSUPPORTED, "line transforms: too many lines");
     mr::LineArgs a = base;
     a.in = in;
     a.out = out;
     a.inverse = inverse ? 1 : 0;
     if (mr::mr_line_launch(big, a, (int)lines, (size_t)a.pl.n * sizeof(double2), st))
-        return slm_set_error(SLM_ERR_HIP, "line transform launch failed");
+        return fail(SLM_ERR_HIP, "line transform launch failed");
     return 0;
 }
 
 // out = op(in): forward or inverse (unscaled) 2-D transform of [B][H][W]
 // complex128 as rows -> transpose -> rows -> transpose; in may equal out
-int dft2(GenericEngine* g, const GenericView& v, const double2* in, double2* out, bool inverse) {
+int dft2(GenericEngine* g, const PlanState& v, const double2* in, double2* out, bool inverse) {
     hipStream_t st = v.stream;
     if (int rc = line_pass(g, g->lw, g->big_w, in, g->tmp, (long long)v.B * v.H, inverse, st)) return rc;
     hipLaunchKernelGGL(k_transpose, dim3((v.W + 31) / 32, (v.H + 31) / 32, v.B), dim3(256), 0, st, g->tmp, g->tmp2,
@@ -381,7 +403,7 @@ int dft2(GenericEngine* g, const GenericView& v, const double2* in, double2* out
     return 0;
 }
 
-StatsParams stats_of(const GenericView& v, double tol, int iter) {
+StatsParams stats_of(const PlanState& v, double tol, int iter) {
     StatsParams s{};
     s.partials = v.partials;
     s.stats = v.stats;
@@ -510,7 +532,7 @@ MrTiling mr_tiling(int B, int H, int W) {
 // twiddles exp(-2 pi i t / n) and the DIF output order's natural indices
 int mr_plan_line(GenericEngine* g, int n, mr::LinePlan* pl, hipStream_t st, std::vector<int>* rev_out = nullptr) {
     std::vector<int> rad;
-    if (!mr_radices(n, rad)) return slm_set_error(SLM_ERR_UNSUPPORTED, "mixed radix: unsupported length");
+    if (!mr_radices(n, rad)) return fail(SLM_ERR_UNSUPPORTED, "mixed radix: unsupported length");
     pl->n = n;
     pl->np = (int)rad.size();
     for (int i = 0; i < pl->np; ++i) pl->radix[i] = rad[i];
@@ -533,9 +555,9 @@ int mr_plan_line(GenericEngine* g, int n, mr::LinePlan* pl, hipStream_t st, std:
         rev[e] = k;
     }
     void *dtw = nullptr, *drev = nullptr;
-    if (hipMalloc(&dtw, tw.size() * sizeof(double)) != hipSuccess) return slm_set_error(SLM_ERR_HIP, "mixed radix: allocation");
+    if (hipMalloc(&dtw, tw.size() * sizeof(double)) != hipSuccess) return fail(SLM_ERR_HIP, "mixed radix: allocation");
     g->tables.push_back(dtw);
-    if (hipMalloc(&drev, rev.size() * sizeof(int)) != hipSuccess) return slm_set_error(SLM_ERR_HIP, "mixed radix: allocation");
+    if (hipMalloc(&drev, rev.size() * sizeof(int)) != hipSuccess) return fail(SLM_ERR_HIP, "mixed radix: allocation");
     g->tables.push_back(drev);
     G_HIP(hipMemcpyAsync(dtw, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, st));
     G_HIP(hipMemcpyAsync(drev, rev.data(), rev.size() * sizeof(int), hipMemcpyHostToDevice, st));
@@ -577,9 +599,9 @@ int line_plan(GenericEngine* g, int n, bool chirp_z, mr::LineArgs* la, bool* big
     };
     while (!smooth5(M)) ++M;
     if (M > mr::kMaxLine)
-        return slm_set_error(SLM_ERR_UNSUPPORTED,
-                             "unsupported side: a side over 4096 with a prime factor above 13, or any side over "
-                             "8192, does not fit one workgroup's chirp-z line (8192 points)");
+        return fail(SLM_ERR_UNSUPPORTED,
+                    "unsupported side: a side over 4096 with a prime factor above 13, or any side over "
+                    "8192, does not fit one workgroup's chirp-z line (8192 points)");
     std::vector<int> rev;
     if (int rc = mr_plan_line(g, M, &la->pl, st, &rev)) return rc;
     la->direct = 0;
@@ -623,9 +645,9 @@ int line_plan(GenericEngine* g, int n, bool chirp_z, mr::LineArgs* la, bool* big
         bh[(size_t)e * 2 + 1] = bhat[(size_t)rev[e] * 2 + 1];
     }
     void *dc = nullptr, *db = nullptr;
-    if (hipMalloc(&dc, chirp.size() * sizeof(double)) != hipSuccess) return slm_set_error(SLM_ERR_HIP, "line transforms: allocation");
+    if (hipMalloc(&dc, chirp.size() * sizeof(double)) != hipSuccess) return fail(SLM_ERR_HIP, "line transforms: allocation");
     g->tables.push_back(dc);
-    if (hipMalloc(&db, bh.size() * sizeof(double)) != hipSuccess) return slm_set_error(SLM_ERR_HIP, "line transforms: allocation");
+    if (hipMalloc(&db, bh.size() * sizeof(double)) != hipSuccess) return fail(SLM_ERR_HIP, "line transforms: allocation");
     g->tables.push_back(db);
     G_HIP(hipMemcpyAsync(dc, chirp.data(), chirp.size() * sizeof(double), hipMemcpyHostToDevice, st));
     G_HIP(hipMemcpyAsync(db, bh.data(), bh.size() * sizeof(double), hipMemcpyHostToDevice, st));
@@ -642,7 +664,7 @@ int mr_roots(hipStream_t st) {
             const double ang = 2.0 * M_PI * (double)q / (double)R;
             roots[R * mr::kMaxRadix + q] = make_double2(std::cos(ang), -std::sin(ang));
         }
-    if (mr::mr_set_roots(roots.data(), st)) return slm_set_error(SLM_ERR_HIP, "mixed radix: root table upload failed");
+    if (mr::mr_set_roots(roots.data(), st)) return fail(SLM_ERR_HIP, "mixed radix: root table upload failed");
     return 0;
 }
 
@@ -773,9 +795,9 @@ int rz_plan_line(GenericEngine* g, int key, mr::LinePlan* pl, hipStream_t st) {
     const bool f32 = g->prec == PREC_F32;
     const size_t tw_bytes = f32 ? twf.size() * sizeof(float) : tw.size() * sizeof(double);
     void *dtw = nullptr, *drev = nullptr;
-    if (hipMalloc(&dtw, tw_bytes) != hipSuccess) return slm_set_error(SLM_ERR_HIP, "radix plans: allocation");
+    if (hipMalloc(&dtw, tw_bytes) != hipSuccess) return fail(SLM_ERR_HIP, "radix plans: allocation");
     g->tables.push_back(dtw);
-    if (hipMalloc(&drev, rev.size() * sizeof(int)) != hipSuccess) return slm_set_error(SLM_ERR_HIP, "radix plans: allocation");
+    if (hipMalloc(&drev, rev.size() * sizeof(int)) != hipSuccess) return fail(SLM_ERR_HIP, "radix plans: allocation");
     g->tables.push_back(drev);
     G_HIP(hipMemcpyAsync(dtw, f32 ? (const void*)twf.data() : (const void*)tw.data(), tw_bytes, hipMemcpyHostToDevice,
                          st));
@@ -788,19 +810,20 @@ int rz_plan_line(GenericEngine* g, int key, mr::LinePlan* pl, hipStream_t st) {
     return 0;
 }
 
-// kernel-class marks around a launch (slm_plan_run_timed events)
+// a timed run's event pair around a launch (slm_plan_run_timed; the any-size
+// engine launches directly, so the events are recorded on the plan stream)
 struct Mark {
-    const GenericView& v;
-    int cls;
-    Mark(const GenericView& vv, int c) : v(vv), cls(c) {
-        if (v.mark) v.mark(v.mark_ctx, cls, 1);
+    const PlanState& v;
+    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+    Mark(const PlanState& vv, int cls) : v(vv) {
+        if (v.timing && !v.timing->next(cls, &ev)) (void)hipEventRecord(ev->first, v.stream);
     }
     ~Mark() {
-        if (v.mark) v.mark(v.mark_ctx, cls, 0);
+        if (ev) (void)hipEventRecord(ev->second, v.stream);
     }
 };
 
-int mr_row(GenericEngine* g, const GenericView& v, int op, mr::RowArgs a, int cls = SLM_KERNEL_OTHER) {
+int mr_row(GenericEngine* g, const PlanState& v, int op, mr::RowArgs a, int cls = SLM_KERNEL_OTHER) {
     a.pl = g->pw;
     a.B = v.B;
     a.H = v.H;
@@ -818,15 +841,15 @@ int mr_row(GenericEngine* g, const GenericView& v, int op, mr::RowArgs a, int cl
         // an unchecked run's iterations before the last never take the phase branch
         if (op == mr::RO_GS && !a.checked && !a.last) op = mr::RO_GS_MID;
         if (rz::rz_row_launch(g->rkey, g->prec, g->rz_lay, op, a, grid, v.stream))
-            return slm_set_error(SLM_ERR_HIP, "radix-plan row launch failed");
+            return fail(SLM_ERR_HIP, "radix-plan row launch failed");
         return 0;
     }
     if (mr::mr_row_launch(op, g->big, a, grid, lds, v.stream))
-        return slm_set_error(SLM_ERR_HIP, "mixed-radix row launch failed");
+        return fail(SLM_ERR_HIP, "mixed-radix row launch failed");
     return 0;
 }
 
-int mr_col(GenericEngine* g, const GenericView& v, int op, mr::ColArgs a, int cls = SLM_KERNEL_OTHER) {
+int mr_col(GenericEngine* g, const PlanState& v, int op, mr::ColArgs a, int cls = SLM_KERNEL_OTHER) {
     a.pl = g->ph;
     a.B = v.B;
     a.H = v.H;
@@ -849,16 +872,16 @@ int mr_col(GenericEngine* g, const GenericView& v, int op, mr::ColArgs a, int cl
     if (g->rz) {
         if (op == mr::CO_GD_GRAD && v.tt == TGT_U8) op = mr::CO_GD_GRAD_U8;
         if (rz::rz_col_launch(g->ckey, g->prec, g->rz_lay, g->rz_cw, op, a, grid, v.stream))
-            return slm_set_error(SLM_ERR_HIP, "radix-plan column launch failed");
+            return fail(SLM_ERR_HIP, "radix-plan column launch failed");
         return 0;
     }
     if (mr::mr_col_launch(op, g->big, a, grid, lds, v.stream))
-        return slm_set_error(SLM_ERR_HIP, "mixed-radix column launch failed");
+        return fail(SLM_ERR_HIP, "mixed-radix column launch failed");
     return 0;
 }
 
 // out = fft2 / unscaled ifft2 of in (device complex128 [B][H][W]; in may equal out)
-int mr_fft2(GenericEngine* g, const GenericView& v, const double2* in, double2* out, bool inverse) {
+int mr_fft2(GenericEngine* g, const PlanState& v, const double2* in, double2* out, bool inverse) {
     mr::RowArgs r;
     r.in = in;
     r.out = g->a;
@@ -869,7 +892,7 @@ int mr_fft2(GenericEngine* g, const GenericView& v, const double2* in, double2* 
     return mr_col(g, v, inverse ? mr::CO_INV : mr::CO_FWD, c);
 }
 
-int mr_enqueue(GenericEngine* g, const GenericView& v, int loops, double tol, int checked, float wa, bool phase_set,
+int mr_enqueue(GenericEngine* g, const PlanState& v, int loops, double tol, int checked, float wa, bool phase_set,
                bool field_set) {
     const long long n = (long long)v.B * v.holo;
     const int grid = grid_of(n);
@@ -966,17 +989,9 @@ int generic_nwg(int B, int H, int W, long long holo, int algo, int prec) {
     return (int)std::max<long long>(1, std::min<long long>(1024, holo / (kGT * 8)));
 }
 
-bool generic_uses_blas(const GenericEngine* g) {
-    (void)g;  // no vendor library calls on any back end since r06: every run is graph-captured
-    return false;
-}
-
-int generic_kind(const GenericEngine* g) {  // 2: line transforms
-    return !g ? -1 : g->rz ? (g->prec == PREC_F32 ? 5 : 4) : g->mr ? 3 : 2;
-}
-
-void generic_info(const GenericEngine* g, int info[8]) {
-    info[0] = generic_kind(g);
+int GenericEngine::generic_info(int info[8]) const {
+    const GenericEngine* g = this;
+    info[0] = kind();
     info[1] = g->prec;
     info[2] = g->rz ? g->rkey : -1;
     info[3] = g->rz ? g->ckey : -1;
@@ -984,24 +999,24 @@ void generic_info(const GenericEngine* g, int info[8]) {
     info[5] = g->rz ? g->rz_cw : g->mr ? 1 << g->cw_log2 : 1;
     info[6] = g->rz ? g->rz_lay : 0;
     info[7] = g->mr ? g->nwg_col : 0;
+    return 0;
 }
 
-void generic_destroy(GenericEngine* g) {
-    if (!g) return;
+GenericEngine::~GenericEngine() {
+    GenericEngine* g = this;
     for (void* p : {(void*)g->a, (void*)g->b, (void*)g->d, (void*)g->x, (void*)g->tmp, (void*)g->tmp2})
         if (p) (void)hipFree(p);
     for (void* p : g->tables)
         if (p) (void)hipFree(p);
     if (g->ain_rev) (void)hipFree(g->ain_rev);
     if (g->tgt_blk) (void)hipFree(g->tgt_blk);
-    delete g;
 }
 
-int generic_create(const GenericView& v, GenericEngine** out) {
+int generic_create(const PlanState& v, Engine** out) {
     *out = nullptr;
     GenericEngine* g = new GenericEngine();
     auto fail_free = [&](int rc) {
-        generic_destroy(g);
+        delete g;
         return rc;
     };
     const size_t n = (size_t)v.B * v.holo;
@@ -1019,15 +1034,15 @@ int generic_create(const GenericView& v, GenericEngine** out) {
         g->rz_lay = rc.lay;
         g->nwg_col = v.W / rc.cw;
         g->rpw = rz::rz_row_rpw(rc.rkey, rc.lay);
-        if (g->nwg_col != v.nwg) return fail_free(slm_set_error(SLM_ERR_STATE, "radix c128: partial-slab mismatch"));
+        if (g->nwg_col != v.nwg) return fail_free(fail(SLM_ERR_STATE, "radix c128: partial-slab mismatch"));
         if (!alloc(&g->a, n) || !alloc(&g->b, n) || (v.algo == SLM_ALGO_GD && !alloc(&g->x, n)) ||
             (v.has_ain && hipMalloc((void**)&g->ain_rev, (size_t)v.holo * sizeof(float)) != hipSuccess) ||
             hipMalloc((void**)&g->tgt_blk, n * sizeof(float)) != hipSuccess)
-            return fail_free(slm_set_error(SLM_ERR_HIP, "radix c128: device allocation failed"));
+            return fail_free(fail(SLM_ERR_HIP, "radix c128: device allocation failed"));
         if (int e = rz_plan_line(g, rc.rkey, &g->pw, v.stream)) return fail_free(e);
         if (int e = rz_plan_line(g, rc.ckey, &g->ph, v.stream)) return fail_free(e);
         if (hipMemsetAsync(g->a, 0, n * sizeof(double2), v.stream) != hipSuccess)
-            return fail_free(slm_set_error(SLM_ERR_HIP, "radix c128: state initialisation failed"));
+            return fail_free(fail(SLM_ERR_HIP, "radix c128: state initialisation failed"));
         *out = g;
         return 0;
     }
@@ -1038,22 +1053,22 @@ int generic_create(const GenericView& v, GenericEngine** out) {
         g->cw_log2 = t.cw_log2;
         g->nwg_col = (v.W + (1 << g->cw_log2) - 1) >> g->cw_log2;
         g->rpw = t.rpw;
-        if (g->nwg_col != v.nwg) return fail_free(slm_set_error(SLM_ERR_STATE, "mixed radix: partial-slab mismatch"));
+        if (g->nwg_col != v.nwg) return fail_free(fail(SLM_ERR_STATE, "mixed radix: partial-slab mismatch"));
         if (!alloc(&g->a, n) || !alloc(&g->b, n) || (v.algo == SLM_ALGO_GD && !alloc(&g->x, n)) ||
             (v.has_ain && hipMalloc((void**)&g->ain_rev, (size_t)v.holo * sizeof(float)) != hipSuccess))
-            return fail_free(slm_set_error(SLM_ERR_HIP, "mixed radix: device allocation failed"));
+            return fail_free(fail(SLM_ERR_HIP, "mixed radix: device allocation failed"));
         if (int rc = mr_plan_line(g, v.W, &g->pw, v.stream)) return fail_free(rc);
         if (int rc = mr_plan_line(g, v.H, &g->ph, v.stream)) return fail_free(rc);
         if (int rc = mr_roots(v.stream)) return fail_free(rc);
         // the state is defined before any run (read_field of a fresh plan is refused upstream)
         if (hipMemsetAsync(g->a, 0, n * sizeof(double2), v.stream) != hipSuccess)
-            return fail_free(slm_set_error(SLM_ERR_HIP, "mixed radix: state initialisation failed"));
+            return fail_free(fail(SLM_ERR_HIP, "mixed radix: state initialisation failed"));
         *out = g;
         return 0;
     }
     if (!alloc(&g->a, n) || !alloc(&g->b, n) || !alloc(&g->d, n) || !alloc(&g->tmp, n) || !alloc(&g->tmp2, n) ||
         (v.algo == SLM_ALGO_GD && !alloc(&g->x, n)))
-        return fail_free(slm_set_error(SLM_ERR_HIP, "line transforms: device allocation failed"));
+        return fail_free(fail(SLM_ERR_HIP, "line transforms: device allocation failed"));
     const bool chirp_all = mr_forced_lines();
     if (int rc = line_plan(g, v.W, chirp_all, &g->lw, &g->big_w, v.stream)) return fail_free(rc);
     if (int rc = line_plan(g, v.H, chirp_all, &g->lh, &g->big_h, v.stream)) return fail_free(rc);
@@ -1062,8 +1077,9 @@ int generic_create(const GenericView& v, GenericEngine** out) {
     return 0;
 }
 
-int generic_enqueue(GenericEngine* g, const GenericView& v, int loops, double tol, int checked, float wa,
-                    bool phase_set, bool field_set) {
+int GenericEngine::enqueue(PlanState& v, int loops, double tol, int checked, float wa, bool phase_set,
+                           bool field_set) {
+    GenericEngine* g = this;
     if (g->mr) return mr_enqueue(g, v, loops, tol, checked, wa, phase_set, field_set);
     const long long n = (long long)v.B * v.holo;
     const int grid = grid_of(n);
@@ -1117,8 +1133,9 @@ int generic_enqueue(GenericEngine* g, const GenericView& v, int loops, double to
     return 0;
 }
 
-int generic_field(GenericEngine* g, const GenericView& v, float2* out) {
-    if (!g->x) return slm_set_error(SLM_ERR_STATE, "the field is the state of GD plans");
+int GenericEngine::field_c64(const PlanState& v, float2* out) {
+    GenericEngine* g = this;
+    if (!g->x) return fail(SLM_ERR_STATE, "the field is the state of GD plans");
     const long long n = (long long)v.B * v.holo;
     if (g->mr)  // rows in digit-reversed order
         hipLaunchKernelGGL(k_c128_to_c64_rev, dim3(grid_of(n)), dim3(kGT), 0, v.stream, g->x, out, g->pw.rev, v.W, n);
@@ -1128,7 +1145,8 @@ int generic_field(GenericEngine* g, const GenericView& v, float2* out) {
     return 0;
 }
 
-int generic_fft2(GenericEngine* g, const GenericView& v, const float2* in, float2* out, int inverse) {
+int GenericEngine::fft2_c64(const PlanState& v, const float2* in, float2* out, int inverse) {
+    GenericEngine* g = this;
     const long long n = (long long)v.B * v.holo;
     if (g->prec == PREC_F32)  // complex64 radix kernels: straight on the caller's buffers
         return mr_fft2(g, v, reinterpret_cast<const double2*>(in), reinterpret_cast<double2*>(out), inverse != 0);
@@ -1139,7 +1157,10 @@ int generic_fft2(GenericEngine* g, const GenericView& v, const float2* in, float
     return 0;
 }
 
-int generic_intensity(GenericEngine* g, const GenericView& v, const float* phase, float* out) {
+int GenericEngine::intensity(PlanState& v) {
+    GenericEngine* g = this;
+    const float* phase = v.phase_in;
+    float* out = v.e_out;
     const long long n = (long long)v.B * v.holo;
     if (g->prec == PREC_F32) {
         float2* b = reinterpret_cast<float2*>(g->b);
@@ -1156,9 +1177,47 @@ int generic_intensity(GenericEngine* g, const GenericView& v, const float* phase
     return 0;
 }
 
-int generic_fft2_z(GenericEngine* g, const GenericView& v, const double2* in, double2* out, int inverse) {
-    if (g->prec != PREC_F64) return slm_set_error(SLM_ERR_STATE, "fft2_c128 on a complex64 engine");
+int GenericEngine::fft2_z(PlanState& v, const double2* in, double2* out, int inverse) {
+    GenericEngine* g = this;
+    if (g->prec != PREC_F64) return fail(SLM_ERR_STATE, "fft2_c128 on a complex64 engine");
     return g->mr ? mr_fft2(g, v, in, out, inverse != 0) : dft2(g, v, in, out, inverse != 0);
+}
+
+int GenericEngine::land_field(PlanState& v, const float* field) {
+    HIP_TRY(hipMemcpyAsync(v.field0, field, (size_t)v.B * v.holo * sizeof(float2), hipMemcpyHostToDevice, v.stream));
+    return 0;
+}
+
+int GenericEngine::read_field(PlanState& v, bool fresh, float* field) {
+    if (!fresh) RC(field_c64(v, v.xa));
+    return copy_sync(field, fresh ? v.field0 : v.xa, (size_t)v.B * v.holo * sizeof(float2), hipMemcpyDeviceToHost,
+                     v.stream);
+}
+
+// row-major in place through the plan's staging buffer
+int GenericEngine::fft2(PlanState& v, const float* in, float* out, int inverse) {
+    const size_t bytes = (size_t)v.B * v.holo * sizeof(float2);
+    hipError_t e = hipMemcpyAsync(v.xa, in, bytes, hipMemcpyHostToDevice, v.stream);
+    if (e != hipSuccess) return fail(SLM_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
+    RC(fft2_c64(v, v.xa, v.xa, inverse));
+    return copy_sync(out, v.xa, bytes, hipMemcpyDeviceToHost, v.stream);
+}
+
+long long GenericEngine::kernel_bytes(const PlanState& v, int cls) const {
+    if (kind() == 2) return 0;  // line transforms: no column / row kernel classes
+    // mixed radix / radix plans, complex128 state (complex64: z = 8): column pass
+    // in z + T + out z (GD statistics: in + T); row pass in z + out z (+ a_in)
+    // (+ GD field read and write 2z)
+    const long long px = (long long)v.B * v.holo;
+    const long long tb = v.tt == SLM_TGT_U8 ? 1 : 4;
+    const long long ab = v.has_ain ? 4 : 0;
+    const long long z = v.prec == PREC_F32 ? 8 : 16;
+    switch (cls) {
+        case SLM_KERNEL_COL_MAIN: return px * (2 * z + tb);
+        case SLM_KERNEL_ROW_MAIN: return px * (2 * z + ab + (v.algo == SLM_ALGO_GD ? 2 * z : 0));
+        case SLM_KERNEL_GD_STATS: return px * (z + tb);
+        default: return 0;
+    }
 }
 
 }  // namespace slm
