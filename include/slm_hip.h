@@ -14,6 +14,9 @@
  *                                            "fourier" :153-156)
  *   slm_fft2                              -> scipy.fft.fft2 / ifft2 as called at
  *                                            src/algorithms.py:27,31,34,84,88 (unscaled)
+ *   slm_gsw / slm_plan_* with SLM_ALGO_GSW -> no reference counterpart: GS with Di Leonardo's
+ *                                            per-pixel weight feedback, an addition next to
+ *                                            the drop-in (see "weighted GS" below).
  *   slm_comm_* / slm_plan_gather_phase    -> no reference counterpart: the batch
  *                                            loop of src/generate_hologram_sequence.py:19-31
  *                                            sharded over GPUs, phases gathered over RCCL.
@@ -34,6 +37,8 @@ extern "C" {
 
 #define SLM_ALGO_GS 0
 #define SLM_ALGO_GD 1
+/* weighted Gerchberg-Saxton (uniform trap intensities); no reference counterpart, see below */
+#define SLM_ALGO_GSW 2
 
 #define SLM_TGT_U8 0  /* uint8 target; amplitude = float16(sqrt(T)) as numpy does */
 #define SLM_TGT_F32 1 /* float32 target; amplitude = sqrtf(T) */
@@ -43,7 +48,7 @@ extern "C" {
 #define SLM_PRECISION_F64 1 /* float64 butterflies and twiddles */
 
 /* kernel classes for timing / roofline queries */
-#define SLM_KERNEL_COL_MAIN 0 /* GS column pass, or GD column pass (fused statistics + gradient, or the gradient launch) */
+#define SLM_KERNEL_COL_MAIN 0 /* GS / weighted-GS column pass, or GD column pass (fused statistics + gradient, or the gradient launch) */
 #define SLM_KERNEL_ROW_MAIN 1 /* GS / GD fused row pass */
 #define SLM_KERNEL_GD_STATS 2 /* GD statistics column pass */
 #define SLM_KERNEL_OTHER 3    /* setup, phase extraction, reductions */
@@ -94,6 +99,33 @@ int slm_plan_set_ain(slm_plan* plan, const float* ain);           /* [height][wi
 int slm_plan_set_phase(slm_plan* plan, const float* phase);       /* GS warm start [batch][h][w]; NULL = cold */
 int slm_plan_set_field(slm_plan* plan, const float* field_re_im); /* GD initial x [batch][h][w][2]; NULL = fourier */
 int slm_plan_set_lr(slm_plan* plan, const float* lr);             /* GD learning rate per iteration [max_loops] */
+/* ---- weighted GS (SLM_ALGO_GSW): no reference counterpart ----------------
+ * Per hologram, with the support sup = T > 0, weights g (ones, or the caller's)
+ * and the feedback exponent p >= 0, every GS iteration additionally does
+ *     on sup where |C| > 0:  g *= (a_T / |C|)^p;   D = a_T g C/|C|
+ * (a_T, the start, E, the statistics and the stop test as GS defines them; p = 0
+ * is GS bit for bit, statistics included; with p > 0 the sums behind the error
+ * are taken in float64 against the exact target, because the error of a trap
+ * target made uniform is a ~1e-4 remainder of those sums). Only angle(A) and E leave the loop, so g is defined up to a
+ * positive factor per hologram: the device keeps it near mean 1 over the support
+ * with the previous iteration's sum and clamps it to [2^-40, 2^40] of that scale.
+ * Plans of the fused engine only: both sides one of 64 ... 4096 (powers of two)
+ * or 768; other shapes and $SLM_ENGINE=float64 get SLM_ERR_UNSUPPORTED from
+ * slm_plan_create. slm_plan_set_phase warm-starts such a plan as a GS plan.
+ *
+ * slm_plan_set_feedback: the exponent p (default 1); negative or non-finite
+ *   values give SLM_ERR_ARG.
+ * slm_plan_set_weights: initial weights [batch][h][w], NULL = ones. Call after
+ *   slm_plan_set_target (a new target returns the plan to ones); an entry on the
+ *   support that is not positive and finite gives SLM_ERR_ARG. The plan keeps
+ *   them in a buffer of their own: every run starts from them again.
+ * slm_plan_read_weights: g after the last run (of a stopped hologram: at its
+ *   stop iteration), or the weights set since; scaled to mean 1 over the
+ *   support, exactly 1 off it.
+ * All three give SLM_ERR_STATE on a plan of another algorithm.             */
+int slm_plan_set_feedback(slm_plan* plan, float feedback);
+int slm_plan_set_weights(slm_plan* plan, const float* weights);
+int slm_plan_read_weights(slm_plan* plan, float* weights);
 /* Enqueue one full run (setup + loops iterations + outputs) on the plan's
  * stream. tol as in `while error > tolerance`; checked != 0 evaluates that
  * test on the device after every iteration (required when tol > 0). */
@@ -180,6 +212,11 @@ int slm_gs(const void* tgt, int tgt_type, const float* ain, int batch, int heigh
 int slm_gd(const void* tgt, int tgt_type, const float* ain, int batch, int height, int width, int max_loops,
            double tol, const float* init_field, const float* lr, float white_attention, float* out_phase,
            float* out_expected, double* out_stats, int* out_iters);
+/* weighted GS (no reference counterpart): slm_gs's arguments, then the feedback
+ * exponent, the initial weights (NULL = ones) and the weights out (may be NULL) */
+int slm_gsw(const void* tgt, int tgt_type, const float* ain, int batch, int height, int width, int max_loops,
+            double tol, const float* init_phase, float* out_phase, float* out_expected, double* out_stats,
+            int* out_iters, float feedback, const float* init_weights, float* out_weights);
 
 /* One process, several GPUs (SURVEY.md 8b's slm_gs_multi): the batch is cut
  * into n_gpus contiguous shards (the first batch % n_gpus one hologram larger,
@@ -192,7 +229,12 @@ int slm_gd(const void* tgt, int tgt_type, const float* ain, int batch, int heigh
 int slm_gs_multi(int n_gpus, const int* devices, const void* tgt, int tgt_type, const float* ain, int batch,
                  int height, int width, int max_loops, double tol, const float* init_phase, float* out_phase,
                  float* out_expected, double* out_stats, int* out_iters);
-/* Per-shard timing of the calling process's last slm_gs_multi: wall_ms[r] =
+/* The same for weighted GS (no reference counterpart): every shard starts from
+ * weights of one; the weights themselves stay on the shards. */
+int slm_gsw_multi(int n_gpus, const int* devices, const void* tgt, int tgt_type, const float* ain, int batch,
+                  int height, int width, int max_loops, double tol, const float* init_phase, float* out_phase,
+                  float* out_expected, double* out_stats, int* out_iters, float feedback);
+/* Per-shard timing of the calling process's last slm_gs_multi / slm_gsw_multi: wall_ms[r] =
  * shard r's whole thread (plan, upload, run, read back), run_ms[r] = its run
  * alone (enqueue to stream drained); up to max_shards values each (either
  * pointer may be NULL). Returns the number of shards of that call (0 if none). */

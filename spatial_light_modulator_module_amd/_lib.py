@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("SLM_LIB_PATH") or os.path.join(os.path.dirname(os.pat
 
 ALGO_GS = 0
 ALGO_GD = 1
+ALGO_GSW = 2  # weighted GS: no reference counterpart (include/slm_hip.h)
 TGT_U8 = 0
 TGT_F32 = 1
 PRECISION_F32 = 0
@@ -40,6 +41,14 @@ SUPPORTED_LENGTHS = (64, 128, 256, 512, 768, 1024, 2048, 4096)
 
 class SlmError(RuntimeError):
     """A libslm_hip call failed (message from slm_last_error)."""
+
+    code = 0  # the library's return code (ERR_*), set by check()
+
+
+ERR_ARG = -1
+ERR_HIP = -2
+ERR_UNSUPPORTED = -3
+ERR_STATE = -4
 
 
 _c_int = ctypes.c_int
@@ -66,6 +75,9 @@ _SIGNATURES = [
     ("slm_plan_set_phase", _c_int, [_vp, _vp]),
     ("slm_plan_set_field", _c_int, [_vp, _vp]),
     ("slm_plan_set_lr", _c_int, [_vp, _vp]),
+    ("slm_plan_set_feedback", _c_int, [_vp, _c_float]),
+    ("slm_plan_set_weights", _c_int, [_vp, _vp]),
+    ("slm_plan_read_weights", _c_int, [_vp, _vp]),
     ("slm_plan_run", _c_int, [_vp, _c_int, _c_double, _c_int, _c_float]),
     ("slm_plan_run_timed", _c_int, [_vp, _c_int, _c_double, _c_int, _c_float, _vp, _vp]),
     ("slm_plan_sync", _c_int, [_vp]),
@@ -84,11 +96,15 @@ _SIGNATURES = [
     ("slm_plan_device", _c_int, [_vp]),
     ("slm_plan_read_trace", _c_int, [_vp, _c_int, _vp]),
     ("slm_gs", _c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_double, _vp, _vp, _vp, _vp, _vp]),
+    ("slm_gsw", _c_int, [_vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_double, _vp, _vp, _vp, _vp, _vp,
+                         _c_float, _vp, _vp]),
     ("slm_gd", _c_int,
      [_vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_double, _vp, _vp, _c_float, _vp, _vp, _vp, _vp]),
     ("slm_fft2", _c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int]),
     ("slm_gs_multi", _c_int, [_c_int, _vp, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_double, _vp, _vp,
                               _vp, _vp, _vp]),
+    ("slm_gsw_multi", _c_int, [_c_int, _vp, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_double, _vp, _vp,
+                               _vp, _vp, _vp, _c_float]),
     ("slm_gs_multi_timing", _c_int, [_c_int, _vp, _vp]),
     ("slm_comm_unique_id", _c_int, [_vp]),
     ("slm_comm_init", _c_int, [_c_int, _c_int, _vp]),
@@ -143,7 +159,9 @@ def last_error() -> str:
 
 def check(rc: int, what: str) -> None:
     if rc != 0:
-        raise SlmError(f"{what} failed ({rc}): {last_error()}")
+        err = SlmError(f"{what} failed ({rc}): {last_error()}")
+        err.code = rc
+        raise err
 
 
 def ptr(a: np.ndarray | None) -> int | None:
@@ -262,6 +280,22 @@ class Plan:
         if a.size != self.max_loops:
             raise ValueError(f"need {self.max_loops} learning rates, got {a.size}")
         check(self._lib.slm_plan_set_lr(self.handle, ptr(a)), "slm_plan_set_lr")
+
+    def set_feedback(self, feedback: float) -> None:
+        """Weighted GS: the exponent p of g *= (a_T / |C|)^p (slm_plan_set_feedback)."""
+        check(self._lib.slm_plan_set_feedback(self.handle, float(feedback)), "slm_plan_set_feedback")
+
+    def set_weights(self, weights: np.ndarray | None) -> None:
+        """Weighted GS: initial weights [batch][h][w], None = ones (slm_plan_set_weights)."""
+        a = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(self.shape)
+        check(self._lib.slm_plan_set_weights(self.handle, ptr(a)), "slm_plan_set_weights")
+
+    def read_weights(self) -> np.ndarray:
+        """Weighted GS: the weights after the last run, mean 1 over the support
+        (T > 0) and exactly 1 off it (slm_plan_read_weights)."""
+        out = np.empty(self.shape, np.float32)
+        check(self._lib.slm_plan_read_weights(self.handle, ptr(out)), "slm_plan_read_weights")
+        return out
 
     def run(self, loops: int, tol: float = 0.0, checked: bool = False, white_attention: float = 0.0) -> None:
         check(self._lib.slm_plan_run(self.handle, loops, float(tol), int(bool(checked)), float(white_attention)),
@@ -476,9 +510,10 @@ def fft2_intensity(phase) -> np.ndarray:
     return out
 
 
-def gs_multi(targets, loops, devices, tol=0.0, ain=None, initial_phase=None):
+def gs_multi(targets, loops, devices, tol=0.0, ain=None, initial_phase=None, feedback=None):
     """slm_gs_multi: GS on a batch [B][H][W] sharded over `devices` (device ids,
-    may repeat) from one process. Returns (phase, expected, stats, iters)."""
+    may repeat) from one process. Returns (phase, expected, stats, iters).
+    With a feedback exponent: weighted GS (slm_gsw_multi)."""
     t = np.asarray(targets)
     tt = TGT_U8 if t.dtype == np.uint8 else TGT_F32
     t = np.ascontiguousarray(t, dtype=np.uint8 if tt == TGT_U8 else np.float32)
@@ -491,9 +526,35 @@ def gs_multi(targets, loops, devices, tol=0.0, ain=None, initial_phase=None):
     stats = np.empty((b, loops, 4), np.float64)
     iters = np.empty(b, np.int32)
     init()
-    check(load().slm_gs_multi(int(dev.size), ptr(dev), ptr(t), tt, ptr(a), b, h, w, int(loops), float(tol), ptr(ph0),
-                              ptr(phase), ptr(expected), ptr(stats), ptr(iters)), "slm_gs_multi")
+    if feedback is None:
+        check(load().slm_gs_multi(int(dev.size), ptr(dev), ptr(t), tt, ptr(a), b, h, w, int(loops), float(tol),
+                                  ptr(ph0), ptr(phase), ptr(expected), ptr(stats), ptr(iters)), "slm_gs_multi")
+    else:
+        check(load().slm_gsw_multi(int(dev.size), ptr(dev), ptr(t), tt, ptr(a), b, h, w, int(loops), float(tol),
+                                   ptr(ph0), ptr(phase), ptr(expected), ptr(stats), ptr(iters), float(feedback)),
+              "slm_gsw_multi")
     return phase, expected, stats, iters
+
+
+def gsw(targets, loops, feedback=1.0, tol=0.0, ain=None, initial_phase=None, initial_weights=None):
+    """slm_gsw: one-shot weighted GS on a batch [B][H][W]. Returns (phase,
+    expected, stats, iters, weights)."""
+    t = np.asarray(targets)
+    tt = TGT_U8 if t.dtype == np.uint8 else TGT_F32
+    t = np.ascontiguousarray(t, dtype=np.uint8 if tt == TGT_U8 else np.float32)
+    b, h, w = t.shape
+    a = None if ain is None else np.ascontiguousarray(ain, dtype=np.float32).reshape(h, w)
+    ph0 = None if initial_phase is None else np.ascontiguousarray(initial_phase, dtype=np.float32).reshape(b, h, w)
+    w0 = None if initial_weights is None else np.ascontiguousarray(initial_weights, dtype=np.float32).reshape(b, h, w)
+    phase = np.empty((b, h, w), np.float32)
+    expected = np.empty((b, h, w), np.float32)
+    stats = np.empty((b, loops, 4), np.float64)
+    iters = np.empty(b, np.int32)
+    weights = np.empty((b, h, w), np.float32)
+    init()
+    check(load().slm_gsw(ptr(t), tt, ptr(a), b, h, w, int(loops), float(tol), ptr(ph0), ptr(phase), ptr(expected),
+                         ptr(stats), ptr(iters), float(feedback), ptr(w0), ptr(weights)), "slm_gsw")
+    return phase, expected, stats, iters, weights
 
 
 def gather_layout(counts, per_item: int) -> np.ndarray:

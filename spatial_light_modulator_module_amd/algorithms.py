@@ -35,6 +35,11 @@ Engines and the cost model (see DESIGN.md sections 1, 3 and 5):
 
 A float64 target is carried as float32 on the device, with its max and sum of
 squares (the error's constant terms) kept exact in float64.
+
+Beyond the reference: ``weighted_gerchberg_saxton(demanded_output, args)`` and
+``run_gsw`` run GS with a per-pixel weight feedback that evens out trap
+intensities ("Weighted GS"), on the fused kernels' shapes
+only. Nothing of the drop-in changes with it.
 """
 from __future__ import annotations
 
@@ -46,7 +51,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from ._lib import ALGO_GD, ALGO_GS, TGT_F32, TGT_U8
+from ._lib import ALGO_GD, ALGO_GS, ALGO_GSW, TGT_F32, TGT_U8
 
 # ---------------------------------------------------------------------------
 # input preparation (reference dtype rules)
@@ -227,9 +232,67 @@ def run_gs(targets, loops, tol=0.0, ain=None, initial_phase=None):
     return _collect(plan, phase, e, stats, iters, loops, checked)
 
 
-def run_gs_multi(targets, loops, devices, tol=0.0, ain=None):
+GSW_SHAPES = ("weighted Gerchberg-Saxton runs on the fused engine only: both sides of the target must be one of "
+              "64, 128, 256, 512, 1024, 2048, 4096 (powers of two) or 768, and $SLM_ENGINE=float64 must not be set")
+
+
+def _check_gsw_shape(h, w):
+    """Weighted GS is built into the fused engine's column pass; the any-size
+    engines (other sides, $SLM_ENGINE=float64) refuse it."""
+    if (h not in _lib.SUPPORTED_LENGTHS or w not in _lib.SUPPORTED_LENGTHS
+            or os.environ.get("SLM_ENGINE") == "float64"):
+        raise ValueError(f"{GSW_SHAPES} (got {h} x {w})")
+
+
+def run_gsw(targets, loops, feedback=1.0, tol=0.0, ain=None, initial_phase=None, initial_weights=None,
+            return_weights=False):
+    """Weighted GS (no reference counterpart; include/slm_hip.h) on a batch
+    [B][H][W]: run_gs's arguments and return values, the feedback exponent p of
+    g *= (a_T / |C|)^p, optional initial weights [B][H][W] and, with
+    return_weights, the weights after the run (mean 1 over the support T > 0,
+    1 off it) appended to the result."""
+    t = np.asarray(targets)
+    tdev, tt = target_for_device(t)
+    b, h, w = tdev.shape
+    _check_gsw_shape(h, w)
+    feedback = float(feedback)
+    if not (np.isfinite(feedback) and feedback >= 0):
+        raise ValueError(f"feedback must be a finite number >= 0, got {feedback}")
+    try:
+        plan = get_plan(ALGO_GSW, b, h, w, tt, ain is not None, loops)
+    except _lib.SlmError as e:
+        if e.code == _lib.ERR_UNSUPPORTED:
+            raise ValueError(f"{GSW_SHAPES} (got {h} x {w})") from e
+        raise
+    plan.set_target(tdev)
+    _exact_target_stats(plan, t)
+    if ain is not None:
+        plan.set_ain(ain)
+    plan.set_feedback(feedback)
+    plan.set_phase(initial_phase)
+    try:
+        plan.set_weights(initial_weights)
+    except _lib.SlmError as e:
+        if e.code == _lib.ERR_ARG:
+            raise ValueError("initial weights must be positive and finite wherever the target is > 0") from e
+        raise
+    checked = tol > 0
+    plan.run(loops, tol, checked)
+    phase, e, stats, iters = plan.read()
+    if not checked:
+        if any(_stop_index(stats[k, :loops, 3], tol) not in (None, loops - 1) for k in range(b)):
+            plan.run(loops, tol, True)
+            phase, e, stats, iters = plan.read()
+            checked = True
+    out = _collect(plan, phase, e, stats, iters, loops, checked)
+    return out + (plan.read_weights(),) if return_weights else out
+
+
+def run_gs_multi(targets, loops, devices, tol=0.0, ain=None, feedback=None):
     """run_gs's contract over several GPUs from this one process
     (slm_gs_multi: contiguous shards, one host thread / plan per device).
+    With a feedback exponent the shards run weighted GS (run_gsw's contract,
+    slm_gsw_multi).
     slm_gs_multi takes the error's constant terms from its float32 copy of the
     target, so frames that float32 does not hold exactly (float64, wide
     integers) go through run_gs, which keeps them in float64 (the two paths
@@ -240,9 +303,11 @@ def run_gs_multi(targets, loops, devices, tol=0.0, ain=None):
             warnings.warn(f"{t.dtype} targets are not exact in float32: the batch runs on this process's one "
                           f"GPU (run_gs) so the error keeps its float64 terms; `devices` {list(devices)} is "
                           "ignored -- pass uint8 or float32 frames to shard them", RuntimeWarning, stacklevel=2)
-        return run_gs(t, loops, tol, ain)
+        return run_gs(t, loops, tol, ain) if feedback is None else run_gsw(t, loops, feedback, tol, ain)
     tdev, _ = target_for_device(t)
-    phase, e, stats, iters = _lib.gs_multi(tdev, loops, devices, tol=tol, ain=ain)
+    if feedback is not None:
+        _check_gsw_shape(*tdev.shape[1:])
+    phase, e, stats, iters = _lib.gs_multi(tdev, loops, devices, tol=tol, ain=ain, feedback=feedback)
     norm = t.reshape(t.shape[0], -1).max(axis=1).astype(np.float64)  # np.amax(demanded_output)
     errs, maxes = [], []
     for k in range(t.shape[0]):
@@ -372,16 +437,52 @@ def gerchberg_saxton(demanded_output, args):
     return hologram, expected_outcome, error_evolution
 
 
-def _gerchberg_saxton_gif(t, args, ain):
+def weighted_gerchberg_saxton(demanded_output, args):
+    """Weighted Gerchberg-Saxton (far field) on the GPU: GS with a per-pixel
+    weight feedback g *= (a_T / |C|)^p on the target's support, which evens out
+    the trap intensities plain GS leaves unequal. No reference counterpart;
+    the return triple, the printed lines and the exceptions are
+    gerchberg_saxton's. Reads ``args.feedback`` (the exponent p, default 1)."""
+    t = np.asarray(demanded_output)
+    h, w = _check_shape(t)
+    _check_gsw_shape(h, w)
+    feedback = float(getattr(args, "feedback", 1.0))
+    ain = incoming_amplitude(args, t.shape)
+    tol = args.tolerance
+    if not _iterations_allowed(args):
+        print()
+        if args.print_info:
+            print()
+            printout(tol + 1, 0, [], args.plot_error)
+        raise UnboundLocalError("local variable 'expected_outcome' referenced before assignment")
+    if args.gif:
+        return _gerchberg_saxton_gif(t, args, ain, feedback)
+    phase, e, errs, norm, emax = run_gsw(t[None], args.max_loops, feedback, tol, ain)
+    error_evolution = errs[0]
+    n = len(error_evolution)
+    _print_loops(n, args.max_loops)
+    if args.print_info:
+        print()
+        printout(error_evolution[-1], n, error_evolution, args.plot_error)
+    return hologram_from(phase[0]), expected_from(e[0], norm[0], emax[0]), error_evolution
+
+
+def _gerchberg_saxton_gif(t, args, ain, feedback=None):
     """GIF frames need intermediate states: run in warm-started chunks that end
-    on every frame iteration (the GS state is angle(A) only)."""
+    on every frame iteration (the GS state is angle(A) only; weighted GS, with
+    a feedback exponent given, also hands its weights from chunk to chunk)."""
     loops, tol, skip = args.max_loops, args.tolerance, args.gif_skip
     phase = None
+    weights = None
     error_evolution = []
     i = 0
     while i < loops:
         step = 1 if i % skip == 0 else min(skip - i % skip, loops - i)
-        ph, e, errs, norm, emax = run_gs(t[None], step, tol, ain, initial_phase=phase)
+        if feedback is None:
+            ph, e, errs, norm, emax = run_gs(t[None], step, tol, ain, initial_phase=phase)
+        else:
+            ph, e, errs, norm, emax, weights = run_gsw(t[None], step, feedback, tol, ain, initial_phase=phase,
+                                                        initial_weights=weights, return_weights=True)
         error_evolution += errs[0]
         phase = ph
         i += len(errs[0])

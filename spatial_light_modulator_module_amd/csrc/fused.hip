@@ -90,6 +90,54 @@ __global__ void fill_int_kernel(int* p, int n, int v) {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = v;
 }
 
+__global__ void fill_float_kernel(float* out, long long n, float v) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        out[i] = v;
+}
+__global__ void copy_float_kernel(const float* in, float* out, long long n) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        out[i] = in[i];
+}
+
+// Weighted GS, off the iteration path. Support statistics of one hologram per
+// workgroup, in a fixed order: the number of support pixels (device target
+// > 0: the uint8 target, or the amplitude of a float32 one) and, with a weight
+// plane w in the same blocked layout, the sum of w over the support; *bad is
+// raised by a support weight that is not positive and finite.
+constexpr int kGswThreads = 1024;
+template <typename TT>
+__global__ void __launch_bounds__(kGswThreads) gsw_support_kernel(const TT* tgt, const float* w, long long holo,
+                                                                   double* count, double* sum, int* bad) {
+    const int b = blockIdx.x;
+    const TT* t = tgt + (long long)b * holo;
+    double mx = 0.0, n = 0.0, sw = 0.0;
+    int flag = 0;
+    for (long long i = threadIdx.x; i < holo; i += kGswThreads) {
+        if (!(t[i] > (TT)0)) continue;
+        n += 1.0;
+        if (w) {
+            const float g = w[(long long)b * holo + i];
+            if (!(g > 0.f && g <= 3.40282347e38f)) flag = 1;
+            sw += (double)g;
+        }
+    }
+    block_reduce_stats<kGswThreads>(mx, n, sw);
+    if (flag && bad) atomicOr(bad, 1);
+    if (threadIdx.x == 0) {
+        if (count) count[b] = n;
+        if (sum) sum[b] = sw;
+    }
+}
+// weights as read back: g count / sum g on the support (mean 1), exactly 1 off it
+template <typename TT>
+__global__ void gsw_normalize_kernel(const TT* tgt, const float* g, float* out, long long holo, long long n,
+                                     const double* count, const double* sum) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const long long b = i / holo;
+        out[i] = tgt[i] > (TT)0 ? (float)((double)g[i] * (count[b] / sum[b])) : 1.f;
+    }
+}
+
 // plog: panel width log2 of the destination / source blocked layout
 // (layout_x_log2(lid): X buffers, the target; layout_y_log2(lid): Y, the GD field)
 // float / complex64 planes of 64-multiple sides move through LDS tiles
@@ -262,10 +310,17 @@ struct FusedEngine : Engine {
     bool fused_pending = false;  // a one-launch GD run is queued and its fault flag not read yet
     float2* y2 = nullptr;        // GD_LIN: column-inverse transform of mask F T
     double* gmax = nullptr;      // GD_LIN: [B][max_loops][nwg] column-workgroup maxima of |F|^2
+    // weighted GS: the running weight plane g (layout X, updated in place by
+    // COL_GSW_MAIN), per hologram the support size and the support sums of the
+    // host-set weights (s.weights0) and of the plane being read back, a flag word
+    float* gw = nullptr;
+    double *gsw_n = nullptr, *gsw_sum0 = nullptr, *gsw_tmp = nullptr;
+    int* gsw_bad = nullptr;
 
     ~FusedEngine() override {
         for (void* ptr : {(void*)xb, (void*)y, (void*)field, (void*)gsync, (void*)gfault, (void*)y2, (void*)gmax,
-                          (void*)trace_col, (void*)trace_row})
+                          (void*)trace_col, (void*)trace_row, (void*)gw, (void*)gsw_n, (void*)gsw_sum0,
+                          (void*)gsw_tmp, (void*)gsw_bad})
             if (ptr) (void)hipFree(ptr);
     }
 
@@ -291,7 +346,7 @@ struct FusedEngine : Engine {
         // iteration, bitwise the same phases: gpurun_out/s11; $SLM_GD_LAYOUT=default
         // keeps the default pair for GD only)
         const char* gl = std::getenv("SLM_GD_LAYOUT");
-        const bool algo_ok = s.algo == SLM_ALGO_GS || !(gl && !std::strcmp(gl, "default"));
+        const bool algo_ok = gs_like(s.algo) || !(gl && !std::strcmp(gl, "default"));
         const bool narrow_ok = algo_ok && row_fn(rk, ROW_GS_MAIN, prow, LAYOUT_NARROW) &&
                                col_fn(ck, w, COL_GS_MAIN, TGT_AMP, prec, LAYOUT_NARROW);
         const char* ls = std::getenv("SLM_LAYOUT");
@@ -408,6 +463,22 @@ struct FusedEngine : Engine {
         ColParams cp = col_params(s);
         cp.loops = loops;
         rp.checked = cp.checked = checked;
+        // weighted GS: the same iteration with COL_GSW_MAIN as its column pass.
+        // Every run starts from the host-set weights (never written by a run) or ones.
+        const bool gsw = s.algo == SLM_ALGO_GSW;
+        const int col_mode = gsw ? COL_GSW_MAIN : COL_GS_MAIN;
+        if (gsw) {
+            const long long n = (long long)s.B * s.holo;
+            const int grid = (int)std::min<long long>(8192, (n + 255) / 256);
+            if (s.weights_set)
+                RC(launch(s, SLM_KERNEL_OTHER, copy_float_kernel, dim3(grid), dim3(256), (const float*)s.weights0, gw, n));
+            else
+                RC(launch(s, SLM_KERNEL_OTHER, fill_float_kernel, dim3(grid), dim3(256), gw, n, 1.f));
+            cp.gw = gw;
+            cp.gsw_n = gsw_n;
+            cp.gsw_sum0 = s.weights_set ? gsw_sum0 : gsw_n;
+            cp.fb = s.feedback;
+        }
         // setup: X0 = rowFFT(a_in A0/|A0|), A0 = ifft2(sqrt T) (src/algorithms.py:14-27),
         // or the warm start B = a_in exp(i phi).
         if (phase_set) {
@@ -432,7 +503,7 @@ struct FusedEngine : Engine {
             cp.out = y;
             cp.iter = i;
             cp.e_blk = (checked || i + 1 == loops) ? e_blk : nullptr;
-            RC(launch_col(s, COL_GS_MAIN, cp, SLM_KERNEL_COL_MAIN));
+            RC(launch_col(s, col_mode, cp, SLM_KERNEL_COL_MAIN));
             if (checked) RC(launch_finalize(s, tol, i));
             if (i + 1 < loops) {
                 rp.in = y;
@@ -550,7 +621,7 @@ struct FusedEngine : Engine {
     }
 
     int enqueue(PlanState& s, int loops, double tol, int checked, float wa, bool phase_set, bool field_set) override {
-        return s.algo == SLM_ALGO_GS ? enqueue_gs(s, loops, tol, checked, phase_set)
+        return gs_like(s.algo) ? enqueue_gs(s, loops, tol, checked, phase_set)
                                      : enqueue_gd(s, loops, tol, checked, wa, field_set);
     }
 
@@ -584,7 +655,61 @@ struct FusedEngine : Engine {
 
     void* target_stage(const PlanState& s) override { return s.e_out; }
 
+    // support statistics of weight plane w (nullptr: the support size alone)
+    int gsw_support(PlanState& s, const float* w, double* count, double* sum, int* bad) {
+        if (s.tt == SLM_TGT_U8)
+            hipLaunchKernelGGL(gsw_support_kernel<uint8_t>, dim3(s.B), dim3(kGswThreads), 0, s.stream,
+                               (const uint8_t*)s.tgt, w, s.holo, count, sum, bad);
+        else
+            hipLaunchKernelGGL(gsw_support_kernel<float>, dim3(s.B), dim3(kGswThreads), 0, s.stream,
+                               (const float*)s.tgt, w, s.holo, count, sum, bad);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+
     int land_target(PlanState& s, const void* staged) override {
+        RC(land_target_layout(s, staged));
+        if (s.algo == SLM_ALGO_GSW) RC(gsw_support(s, nullptr, gsw_n, nullptr, nullptr));
+        return 0;
+    }
+
+    // host float32 [B][H][W] -> s.weights0 (layout X); *bad: an entry on the
+    // support is not positive and finite
+    int land_weights(PlanState& s, const float* w, bool* bad) override {
+        const long long n = (long long)s.B * s.holo;
+        float* const stage = reinterpret_cast<float*>(y);  // scratch between runs
+        HIP_TRY(hipMemcpyAsync(stage, w, (size_t)n * sizeof(float), hipMemcpyHostToDevice, s.stream));
+        RC(relayout(layout_x_log2(lid), (const float*)stage, s.weights0, n, s.H, s.W, true, s.stream));
+        HIP_TRY(hipMemsetAsync(gsw_bad, 0, sizeof(int), s.stream));
+        RC(gsw_support(s, s.weights0, nullptr, gsw_sum0, gsw_bad));
+        int f = 0;
+        RC(copy_sync(&f, gsw_bad, sizeof(int), hipMemcpyDeviceToHost, s.stream));
+        *bad = f != 0;
+        return 0;
+    }
+
+    // the weights to the host, mean 1 over the support and 1 off it: the host-set
+    // plane if `fresh` (set since the last run), else the running plane
+    int read_weights(PlanState& s, bool fresh, float* out) override {
+        const long long n = (long long)s.B * s.holo;
+        const float* src = fresh ? s.weights0 : gw;
+        float* const blk = reinterpret_cast<float*>(y);     // scratch between runs
+        float* const rm = reinterpret_cast<float*>(s.xa);   // (every run rebuilds X from its start state)
+        RC(gsw_support(s, src, gsw_tmp, gsw_tmp + s.B, nullptr));
+        const int grid = (int)std::min<long long>(8192, (n + 255) / 256);
+        if (s.tt == SLM_TGT_U8)
+            hipLaunchKernelGGL(gsw_normalize_kernel<uint8_t>, dim3(grid), dim3(256), 0, s.stream, (const uint8_t*)s.tgt,
+                               src, blk, s.holo, n, gsw_tmp, gsw_tmp + s.B);
+        else
+            hipLaunchKernelGGL(gsw_normalize_kernel<float>, dim3(grid), dim3(256), 0, s.stream, (const float*)s.tgt,
+                               src, blk, s.holo, n, gsw_tmp, gsw_tmp + s.B);
+        HIP_TRY(hipGetLastError());
+        RC(relayout(layout_x_log2(lid), (const float*)blk, rm, n, s.H, s.W, false, s.stream));
+        HIP_TRY(hipStreamSynchronize(s.stream));
+        return copy_sync(out, rm, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s.stream);
+    }
+
+    int land_target_layout(PlanState& s, const void* staged) {
         const long long n = (long long)s.B * s.holo;
         const int xl = layout_x_log2(lid);
         if (s.tt == SLM_TGT_U8)
@@ -657,7 +782,8 @@ struct FusedEngine : Engine {
         const long long ab = s.has_ain ? 4 : 0;
         const bool lin = s.algo == SLM_ALGO_GD && gd_mode == GD_LIN;  // + Y2 out (column) / in (row)
         switch (cls) {
-            case SLM_KERNEL_COL_MAIN: return px * (8 + tb + 8 + (lin ? 8 : 0));  // X (GD: F) in, T in, Y out
+            case SLM_KERNEL_COL_MAIN:  // X (GD: F) in, T in, Y out (+ weighted GS: g in and out)
+                return px * (8 + tb + 8 + (lin ? 8 : 0) + (s.algo == SLM_ALGO_GSW ? 8 : 0));
             case SLM_KERNEL_ROW_MAIN:                                 // Y in, X out (+ a_in) (+ field r/w for GD)
                 return px * (16 + ab + (s.algo == SLM_ALGO_GD ? 16 : 0) + (lin ? 8 : 0));
             case SLM_KERNEL_GD_STATS: return px * (8 + tb);           // X in, T in
@@ -668,7 +794,7 @@ struct FusedEngine : Engine {
     void codes(const PlanState& s, int* col_engine, int* row_engine) const override {
         // mirrors kernels.hpp: kShuffle<K, P> && (CW == 2 | RPW == 2) && one line per thread
         auto shuf = [&](int key, int prec) {
-            return (prec == PREC_F32 || s.algo == SLM_ALGO_GS) && key >= 0 && kPlans[key].n == kShufN &&
+            return (prec == PREC_F32 || gs_like(s.algo)) && key >= 0 && kPlans[key].n == kShufN &&
                    kPlans[key].e == 8;
         };
         *col_engine = shuf(col_key, s.prec) && cw == 2 ? 1 : 0;
@@ -708,6 +834,7 @@ int enqueue_stats_reduce(PlanState& s, int loops, double tol) {
 int fused_create(PlanState& s, Engine** out, int* max_nwg) {
     std::unique_ptr<FusedEngine> f(new FusedEngine());
     // GS keeps a float32 target as its amplitude on the device (land_target)
+    // (weighted GS keeps T itself: its error statistics need the exact target, kernels.hpp)
     f->dev_tt = (s.algo == SLM_ALGO_GS && s.tt == SLM_TGT_F32) ? TGT_AMP : s.tt;
     f->wt_col = s.H >= 2048 ? 0 : 1;
     f->wt_row = ((long long)s.B * s.holo >= (32LL << 20) || s.W >= 4096) ? 0 : 1;
@@ -748,6 +875,13 @@ int fused_create(PlanState& s, Engine** out, int* max_nwg) {
             HIP_TRY(hipMemsetAsync(f->gfault, 0, sizeof(int), s.stream));
             HIP_TRY(hipStreamSynchronize(s.stream));
         }
+    }
+    if (s.algo == SLM_ALGO_GSW) {
+        RC(dev_alloc(&f->gw, n * sizeof(float)));
+        RC(dev_alloc(&f->gsw_n, (size_t)s.B * sizeof(double)));
+        RC(dev_alloc(&f->gsw_sum0, (size_t)s.B * sizeof(double)));
+        RC(dev_alloc(&f->gsw_tmp, (size_t)2 * s.B * sizeof(double)));
+        RC(dev_alloc(&f->gsw_bad, sizeof(int)));
     }
     if (const char* e = std::getenv("SLM_TRACE_BUF"); e && std::atoi(e)) {
         RC(dev_alloc(&f->trace_col, (size_t)s.B * nwg * kTraceSlots * sizeof(unsigned long long)));

@@ -11,6 +11,11 @@
 // loop). Per pixel and iteration this moves 8+8 B per pass plus the target:
 // 36 B (f32 target) or 33 B (u8 target) instead of 68 B for unfused 2-D FFTs.
 //
+// Weighted GS (COL_GSW_MAIN; no reference counterpart) is the same iteration
+// with one float32 weight plane g in the target's layout: the column pass's
+// projection epilogue updates g *= (a_T/|C|)^p on the support and projects with
+// a_T g, reading and writing g in place (+8 B per pixel on that pass).
+//
 // GD (src/algorithms.py:83-93) needs the global max of |F|^2 before the
 // gradient can be formed: its column side is one launch with a grid
 // max-barrier between the forward and the inverse transform where the grid is
@@ -66,7 +71,7 @@ struct ColParams {
     const float2* in_alt;    // GD ping-pong partner (expected-output kernel)
     float2* out;             // column-pass output Y
     const void* tgt;         // target intensity T [B][H][W] (uint8 or float)
-    double* partials;        // [B][max_loops][nwg] x 4 doubles: max, sum E^2, sum E T, 0
+    double* partials;        // [B][max_loops][nwg] x 4 doubles: max, sum E^2, sum E T, 0 (COL_GSW_MAIN: sum g on the support)
     float* e_out;            // |C|^2 of the final iteration [B][H][W]
     float* e_blk;            // COL_EXPECTED: |C|^2 in layout Y (relayout to e_out by the host)
     const int* stop_iter;    // [B]
@@ -90,6 +95,10 @@ struct ColParams {
     int skip_wg_plus1;       // COL_GD_FUSED test knob: workgroup (value - 1) never publishes (0 = off)
     float2* out2;            // COL_GD_LIN: second output (inverse column transform of mask F T)
     double* gmax;            // COL_GD_LIN: [B][max_loops][nwg] workgroup maxima of |F|^2 (dense)
+    float* gw;               // COL_GSW_MAIN: running weights g [B][H][W], layout X (read and written in place)
+    const double* gsw_n;     // COL_GSW_MAIN: [B] support pixels (T > 0) per hologram
+    const double* gsw_sum0;  // COL_GSW_MAIN: [B] sum of g over the support at the start of the run
+    float fb;                // COL_GSW_MAIN: feedback exponent p
 };
 
 enum RowMode : int {
@@ -115,7 +124,8 @@ enum ColMode : int {
     COL_FFT_INV = 6,      // in -> inv -> out (test entry)
     COL_GD_FUSED = 7,     // X -> fwd -> stats, grid barrier (global max) -> mask F (sP - T) -> inv -> Y
     COL_GD_LIN = 8,       // X -> fwd -> stats; mask F P -> inv -> Y, mask F T -> inv -> Y2 (no global max needed)
-    COL_NUM_MODES = 9
+    COL_GSW_MAIN = 9,     // COL_GS_MAIN with the weighted-GS feedback: g *= (a_T/|C|)^p, D = a_T g C/|C|
+    COL_NUM_MODES = 10
 };
 
 // target element types: 0 = uint8 (amplitude rounded to float16 as numpy's
@@ -1077,13 +1087,15 @@ __global__ void __launch_bounds__((ColCfg<K, CW>::THREADS), 1) col_kernel(ColPar
     constexpr int RS = PlanOf<K>::ROWSTRIDE;  // line-major regions (one-group tiles)
     constexpr int SMEM = (ALT ? 2 : 1) * LINE * LW > CW * RS ? (ALT ? 2 : 1) * LINE * LW : CW * RS;
     __shared__ X smem[SMEM];
+    constexpr bool kGsw = MODE == COL_GSW_MAIN;               // weighted GS: the GS pass plus the weight plane
+    constexpr bool kGs = MODE == COL_GS_MAIN || kGsw;         // the GS iteration pass
 
     // a thread carries columns c .. c + L - 1 of the tile (adjacent in the
     // blocked layout: one 16-B access for L = 2)
     // wave-shuffle pair: lane bit 0 selects the column (as here), t per fft_shuffle.hpp
     // (the GS and GD iteration modes)
     constexpr bool SHUF = kShuffle<K, P> && CW == 2 && L == 1 &&
-                          (MODE == COL_GS_MAIN || (P == PREC_F32 && (MODE == COL_GD_STATS || MODE == COL_GD_GRAD ||
+                          (kGs || (P == PREC_F32 && (MODE == COL_GD_STATS || MODE == COL_GD_GRAD ||
                                                                       MODE == COL_GD_FUSED || MODE == COL_GD_LIN)));
     const int c = (threadIdx.x % (CW / L)) * L;
     const int t = SHUF ? shuffle_t(threadIdx.x) : threadIdx.x / (CW / L);
@@ -1098,7 +1110,7 @@ __global__ void __launch_bounds__((ColCfg<K, CW>::THREADS), 1) col_kernel(ColPar
         else
             return LdsT{smem, c};
     }();
-    if constexpr (MODE == COL_GS_MAIN || MODE == COL_GD_GRAD || MODE == COL_GD_FUSED || MODE == COL_GD_LIN)
+    if constexpr (kGs || MODE == COL_GD_GRAD || MODE == COL_GD_FUSED || MODE == COL_GD_LIN)
         trace_entry(p.trace);
     sgpr_pin(p.in, p.out, p.tgt, p.holo, p.nwg, p.B, p.tw, p.checked, p.wt, gridDim.x);
     Twiddles<K, C, tw_mode<P, THREADS, K, true, L>()> tw;
@@ -1109,9 +1121,11 @@ __global__ void __launch_bounds__((ColCfg<K, CW>::THREADS), 1) col_kernel(ColPar
         load_shuffle_tw(stw, threadIdx.x, static_cast<const C*>(p.tw) + twiddle_count_key(K));
     else
         load_twiddles<K, C>(tw, t, p.tw);
-    constexpr bool kTarget = (MODE == COL_GS_MAIN || MODE == COL_GD_STATS || MODE == COL_GD_GRAD ||
+    constexpr bool kTarget = (kGs || MODE == COL_GD_STATS || MODE == COL_GD_GRAD ||
                               MODE == COL_GD_FUSED || MODE == COL_GD_LIN);
     constexpr int NT = kTarget ? E : 1;
+    constexpr int NG = kGsw ? E : 1;
+    float gv[L][NG];  // COL_GSW_MAIN: the tile's weights, loaded with the target, updated in the epilogue
 
     // field / target element (row t + T m, column c + l) of a tile at base
     auto ld_field = [&](const float2* src, long long idx, V (&v)[L][E], int m) {
@@ -1190,17 +1204,51 @@ __global__ void __launch_bounds__((ColCfg<K, CW>::THREADS), 1) col_kernel(ColPar
 #pragma unroll
             for (int m = 0; m < E; ++m) ld_tgt(base + m * kStep, tv, m);
         }
+        if constexpr (kGsw) {  // the weights sit where the target does (layout X)
+#pragma unroll
+            for (int m = 0; m < E; ++m) {
+                if constexpr (L == 2) {
+                    const float2 q = *reinterpret_cast<const float2*>(p.gw + base + m * kStep);
+                    gv[0][m] = q.x;
+                    gv[1][m] = q.y;
+                } else {
+                    gv[0][m] = p.gw[base + m * kStep];
+                }
+            }
+        }
     };
     auto process = [&](long long tile, V (&v)[L][E], float (&tv)[L][NT]) {
         int b, wg;
         long long base;
         where(tile, b, wg, base);
         unsigned long long* const trace =
-            (MODE == COL_GS_MAIN || MODE == COL_GD_GRAD || MODE == COL_GD_FUSED || MODE == COL_GD_LIN) ? p.trace
-                                                                                                       : nullptr;
+            (kGs || MODE == COL_GD_GRAD || MODE == COL_GD_FUSED || MODE == COL_GD_LIN) ? p.trace : nullptr;
         trace_point(trace, tile, 0, false);
         if constexpr (kTarget) {
             if (p.checked && p.iter > p.stop_iter[b]) return;
+        }
+        // Weighted GS: the weights are kept at a one-iteration-stale scale. The
+        // previous launch left sum g over the support in partials[..][3]; every
+        // workgroup folds its hologram's (the same order everywhere: one value per
+        // hologram and iteration) and rescales the weights it reads to mean 1
+        // before it updates them, so g cannot drift out of float32. A positive
+        // scale per hologram changes no output (only angle(A) and E leave the loop).
+        float gscale = 1.f;
+        if constexpr (kGsw) {
+            __shared__ double gsum_sh;
+            double mx0 = 0.0, gs = 0.0, st0 = 0.0;
+            if (p.iter > 0) {
+                const double* part = p.partials + ((long long)b * p.max_loops + (p.iter - 1)) * p.nwg * 4;
+                for (int k = threadIdx.x; k < p.nwg; k += THREADS) gs += part[k * 4 + 3];
+                block_reduce_stats<THREADS>(mx0, gs, st0);
+            } else {
+                gs = p.gsw_sum0[b];
+            }
+            if (threadIdx.x == 0) gsum_sh = gs;
+            lds_barrier();
+            const double tot = gsum_sh;
+            lds_barrier();  // the statistics reduction below reuses the reduction's LDS
+            gscale = (tot > 0.0 && tot < 1e300) ? (float)(p.gsw_n[b] / tot) : 1.f;
         }
         // GD gradient needs this iteration's global max of |F|^2 (src/algorithms.py:86).
         S maxp = 0;
@@ -1331,8 +1379,8 @@ __global__ void __launch_bounds__((ColCfg<K, CW>::THREADS), 1) col_kernel(ColPar
             // checked run) also stores E = |C|^2, the expected output of
             // src/algorithms.py:36, in layout Y (e_blk; relayouted to row-major
             // after the run) -- no separate forward transform for it
-            float* const e_blk = MODE == COL_GS_MAIN ? p.e_blk : nullptr;
-            const long long eb = MODE == COL_GS_MAIN ? out_base(b, wg) : 0;
+            float* const e_blk = kGs ? p.e_blk : nullptr;
+            const long long eb = kGs ? out_base(b, wg) : 0;
             // GS: the thread's partial sums in float32 (its E elements of one
             // column), folded across the workgroup in float64: a few 1e-7 of a
             // partial, averaging out over the hologram's partials (the error's
@@ -1342,22 +1390,71 @@ __global__ void __launch_bounds__((ColCfg<K, CW>::THREADS), 1) col_kernel(ColPar
             // bits, and no float32 overflow for a bright incoming amplitude whose
             // energy sits in a few pixels -- E reaches (holo a_in)^2)
             float mxf = 0.f, s2f = 0.f, stf = 0.f;
-            const float stat_k = MODE == COL_GS_MAIN ? p.stat_k : 1.f;
+            const float stat_k = kGs ? p.stat_k : 1.f;
+            float gsf = 0.f;  // COL_GSW_MAIN: the thread's sum of updated weights on the support
+            const float fb = kGsw ? p.fb : 0.f;
+            // COL_GSW_MAIN with p > 0 sums E^2 and E T in float64 against the exact T
+            // (a weighted-GS plan keeps a float32 target as T, TGT_F32, and takes a_T
+            // from it here): weighted GS makes E proportional to T on a trap target,
+            // the error falls to ~1e-4 of sum T^2 / S, and the expansion (s^2 sum E^2
+            // - 2 s sum E T + sum T^2) / S then cancels by 1e3 .. 3e4 -- float32
+            // partials and T = a_T^2 show at 1e-4 .. 1e-3 of such an error. p = 0 is
+            // GS by definition and reports GS's own sums, bit for bit.
+            double s2d = 0.0, std_ = 0.0;
             auto epi = [&](int l, int m, C& z) {
                 const S e = z.x * z.x + z.y * z.y;
                 const float tl = tv[l][m];
-                if constexpr (MODE == COL_GS_MAIN) {
+                if constexpr (kGs) {
                     const float ef = (float)e;  // |C|^2 as the reference's float64 expected_outcome sees it
                     mxf = fmaxf(mxf, ef);
                     s2f = fmaf(ef * stat_k, ef, s2f);
-                    stf = fmaf(ef, TgtLoad<TT>::intensity(tl), stf);
+                    float ti;  // T as GS's statistics see it (a_T^2 for a float32 target)
+                    if constexpr (kGsw && TT == TGT_F32) {
+                        const float a = TgtLoad<TT>::amp(tl);
+                        ti = a * a;
+                    } else {
+                        ti = TgtLoad<TT>::intensity(tl);
+                    }
+                    stf = fmaf(ef, ti, stf);
+                    if constexpr (kGsw) {
+                        const double ed = (double)ef;
+                        s2d = fma(ed, ed, s2d);
+                        std_ = fma(ed, (double)tl, std_);
+                    }
                 } else if constexpr (MODE == COL_GD_STATS) {
                     const double ed = (double)(float)e;
                     mx = fmax(mx, ed);
                     s2 += ed * ed;
                     st += ed * (double)tl;
                 }
-                if constexpr (MODE == COL_GS_MAIN) {
+                if constexpr (kGsw) {
+                    // g *= (a_T / |C|)^p on the support where |C| > 0, D = a_T g C/|C|.
+                    // The weight read is first brought to mean 1 (gscale) and clamped to
+                    // [2^-40, 2^40] of that scale; the factor is clamped too, so a pixel
+                    // at a zero of C can drive g neither to 0 nor to infinity.
+                    if (e_blk) e_blk[eb + m * kStepY + l] = (float)e;
+                    const float at = TgtLoad<TT>::amp(tl);
+                    float g = gv[l][m];
+                    if (at > 0.f) {
+                        g = fminf(fmaxf(g * gscale, 0x1p-40f), 0x1p40f);
+                        if (fb != 0.f && e > (S)0) {
+                            const S r = (S)at * rsqrt_nr(e);  // a_T / |C|
+                            float f;
+                            if (fb == 1.f)
+                                f = (float)r;
+                            else if (fb == 0.5f)
+                                f = (float)(r * rsqrt_nr(r));  // sqrt(r)
+                            else if constexpr (P == PREC_F32)
+                                f = powf((float)r, fb);
+                            else
+                                f = (float)pow((double)r, (double)fb);
+                            g *= fminf(fmaxf(f, 0x1p-64f), 0x1p64f);
+                        }
+                        gsf += g;
+                    }
+                    gv[l][m] = g;
+                    z = unit_scale(z, (S)at * (S)g);
+                } else if constexpr (MODE == COL_GS_MAIN) {
                     if (e_blk) e_blk[eb + m * kStepY + l] = (float)e;
                     z = unit_scale(z, (S)TgtLoad<TT>::amp(tl));  // D = a_T C/|C| (src/algorithms.py:33)
                 } else if constexpr (MODE == COL_GD_GRAD) {
@@ -1381,21 +1478,43 @@ __global__ void __launch_bounds__((ColCfg<K, CW>::THREADS), 1) col_kernel(ColPar
             else
                 fft_pair<K, false, true, C>(v, t, tw, lds, epi);
             trace_point(trace, tile, 2, false);
-            if constexpr (MODE == COL_GS_MAIN || MODE == COL_GD_GRAD) st_tile(out_base(b, wg), v);
+            if constexpr (kGs || MODE == COL_GD_GRAD) st_tile(out_base(b, wg), v);
+            if constexpr (kGsw) {  // the thread that read a weight writes it back: in place
+#pragma unroll
+                for (int m = 0; m < E; ++m) {
+                    if constexpr (L == 2)
+                        *reinterpret_cast<float2*>(p.gw + base + m * kStep) = make_float2(gv[0][m], gv[1][m]);
+                    else
+                        p.gw[base + m * kStep] = gv[0][m];
+                }
+            }
             // the cross-lane statistics reduction (LDS only) runs while the field stores drain
-            if constexpr (MODE == COL_GS_MAIN) {
+            if constexpr (kGs) {
                 mx = mxf;
                 s2 = (double)s2f / (double)stat_k;  // exact: a power of two
                 st = stf;
             }
-            if constexpr (MODE == COL_GS_MAIN || MODE == COL_GD_STATS) {
+            if constexpr (kGsw) {
+                if (fb != 0.f) {
+                    s2 = s2d;
+                    st = std_;
+                }
+            }
+            if constexpr (kGs || MODE == COL_GD_STATS) {
+                double gsd = 0.0;
+                if constexpr (kGsw) {  // sum g over the tile's support: a fold of its own, ahead of the statistics'
+                    double gs = (double)gsf, z0 = 0.0, z1 = 0.0;
+                    block_reduce_stats<THREADS>(z0, gs, z1);
+                    gsd = gs;
+                    lds_barrier();
+                }
                 block_reduce_stats<THREADS>(mx, s2, st);
                 if (threadIdx.x == 0) {
                     double* dst = p.partials + (((long long)b * p.max_loops + p.iter) * p.nwg + wg) * 4;
                     dst[0] = mx;
                     dst[1] = s2;
                     dst[2] = st;
-                    dst[3] = 0.0;
+                    dst[3] = gsd;
                 }
             }
             trace_point(trace, tile, 3, true);

@@ -47,6 +47,9 @@ struct PlanState {
     float* ain = nullptr;         // incoming amplitude [H][W] or nullptr
     float* phase_in = nullptr;    // GS warm start
     float2* field0 = nullptr;     // GD: host-set initial field, never overwritten by a run
+    float* weights0 = nullptr;    // weighted GS: host-set initial weights, never overwritten by a run
+    bool weights_set = false;     // ... in force (else every run starts from ones)
+    float feedback = 1.f;         // weighted GS: exponent p of g *= (a_T / |C|)^p
     float* lr = nullptr;          // GD learning rate per iteration
     float* phase_out = nullptr;
     float* e_out = nullptr;       // |C|^2 (GS) / |F|^2 (GD) of the last iteration, float32
@@ -62,6 +65,9 @@ struct PlanState {
     EventPool* timing = nullptr;  // a timed run is being enqueued: every launch takes an event pair
 };
 
+// GS and weighted GS share the iteration, the warm start and the float32-target amplitude plane
+inline bool gs_like(int algo) { return algo == SLM_ALGO_GS || algo == SLM_ALGO_GSW; }
+
 struct Engine {
     virtual ~Engine() {}
     // set_target: the upload goes to stage(), then land_target puts it where
@@ -70,6 +76,10 @@ struct Engine {
     virtual int land_target(PlanState& s, const void* staged) = 0;
     // host complex64 [B][H][W] -> s.field0 (enqueued; the caller synchronises)
     virtual int land_field(PlanState& s, const float* field) = 0;
+    // weighted GS (the fused engine only): host float32 [B][H][W] -> s.weights0,
+    // validated on the support; the weights to the host (mean 1 on the support)
+    virtual int land_weights(PlanState& s, const float* w, bool* bad);
+    virtual int read_weights(PlanState& s, bool fresh, float* w);
     // one full run (setup, loops iterations, phase and expected output), on s.stream
     virtual int enqueue(PlanState& s, int loops, double tol, int checked, float wa, bool phase_set,
                         bool field_set) = 0;
@@ -153,6 +163,7 @@ struct slm_plan {
     bool target_set = false, phase_set = false, field_set = false, lr_set = false;
     bool ran = false;          // a run was enqueued (the state buffers hold something)
     bool field_fresh = false;  // set_field since the last run: the plan's field is field0
+    bool weights_fresh = false;  // set_weights since the last run: the plan's weights are weights0 (or ones)
     // parameters of the last enqueued run (settling a faulted run redoes it)
     int last_loops = 0, last_checked = 0;
     double last_tol = 0.0;
@@ -166,7 +177,7 @@ struct slm_plan {
     hipGraphExec_t gexec = nullptr;
     int g_loops = -1, g_checked = -1, g_state = -1;
     double g_tol = 0.0;
-    float g_wa = 0.f;
+    float g_wa = 0.f, g_fb = 0.f;
     slm::GatherState gather;
 };
 

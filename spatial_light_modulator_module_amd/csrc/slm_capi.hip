@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -70,6 +71,12 @@ int Engine::fft2_z(PlanState&, const double2*, double2*, int) {
 }
 int Engine::generic_info(int*) const {
     return fail(SLM_ERR_STATE, "not an any-size plan (fused float32 engine: see slm_plan_info)");
+}
+int Engine::land_weights(PlanState&, const float*, bool*) {
+    return fail(SLM_ERR_STATE, "weights belong to weighted-GS plans of the fused engine");
+}
+int Engine::read_weights(PlanState&, bool, float*) {
+    return fail(SLM_ERR_STATE, "weights belong to weighted-GS plans of the fused engine");
 }
 int Engine::read_trace(PlanState&, int, unsigned long long*) {
     return fail(SLM_ERR_STATE, "no trace buffer (set SLM_TRACE_BUF=1 before creating the plan)");
@@ -203,6 +210,7 @@ int enqueue_run(slm_plan* p, int loops, double tol, int checked, float wa) {
     RC(engine_of(p, &e));
     HIP_TRY(hipSetDevice(p->s.device));
     p->field_fresh = false;  // the run writes the field
+    p->weights_fresh = false;
     p->ran = true;
     RC(enqueue_stop_reset(p->s));
     RC(e->enqueue(p->s, loops, tol, checked, wa, p->phase_set, p->field_set));
@@ -229,7 +237,7 @@ void free_plan(slm_plan* p) {
     gather_free(p->gather);
     for (void* ptr : {(void*)s.xa, s.tgt, (void*)s.ain, (void*)s.phase_in, (void*)s.phase_out, (void*)s.e_out,
                       (void*)s.partials, (void*)s.stats, (void*)s.stop, (void*)s.norm, (void*)s.normf,
-                      (void*)s.sum_t2, (void*)s.field0, (void*)s.lr, (void*)p->ts_part})
+                      (void*)s.sum_t2, (void*)s.field0, (void*)s.lr, (void*)p->ts_part, (void*)s.weights0})
         if (ptr) (void)hipFree(ptr);
     for (auto& e : p->events.pool) {
         (void)hipEventDestroy(e.first);
@@ -247,7 +255,8 @@ int plan_create_on(int device, int algo, int batch, int height, int width, int t
                    int max_loops, slm_plan** out) {
     if (!out) return fail(SLM_ERR_ARG, "null output pointer");
     *out = nullptr;
-    if (algo != SLM_ALGO_GS && algo != SLM_ALGO_GD) return fail(SLM_ERR_ARG, "unknown algorithm %d", algo);
+    if (algo != SLM_ALGO_GS && algo != SLM_ALGO_GD && algo != SLM_ALGO_GSW)
+        return fail(SLM_ERR_ARG, "unknown algorithm %d", algo);
     if (batch < 1 || max_loops < 1) return fail(SLM_ERR_ARG, "batch and max_loops must be >= 1");
     if (tgt_type != SLM_TGT_U8 && tgt_type != SLM_TGT_F32) return fail(SLM_ERR_ARG, "unknown target type");
     if (height < 1 || width < 1) return fail(SLM_ERR_ARG, "image shape %dx%d", height, width);
@@ -266,6 +275,12 @@ int plan_create_on(int device, int algo, int batch, int height, int width, int t
     slm_plan* p = guard.get();
     PlanState& s = p->s;
     p->any_size = forced64 || !slm_supported_length(height) || !slm_supported_length(width);
+    // weighted GS is built into the fused engine's column pass only
+    if (algo == SLM_ALGO_GSW && p->any_size)
+        return fail(SLM_ERR_UNSUPPORTED,
+                    "weighted GS (SLM_ALGO_GSW) runs on the fused engine only: both sides must be one of 64, 128, "
+                    "256, 512, 1024, 2048, 4096 (powers of two) or 768%s; got %d x %d",
+                    forced64 ? ", and SLM_ENGINE=float64 must not be set" : "", height, width);
     s.algo = algo;
     s.B = batch;
     s.H = height;
@@ -282,7 +297,7 @@ int plan_create_on(int device, int algo, int batch, int height, int width, int t
     // <= 3.3e-6 on all six targets (profiles/r06/u8_margin.txt), for ~3 us per
     // iteration. Float32 targets (the bench's) keep float32; $SLM_PRECISION
     // (f32 / f64) overrides both.
-    if (algo == SLM_ALGO_GS && tgt_type == SLM_TGT_U8) s.prec = PREC_F64;
+    if (gs_like(algo) && tgt_type == SLM_TGT_U8) s.prec = PREC_F64;
     if (const char* e = std::getenv("SLM_PRECISION")) s.prec = (std::strcmp(e, "f64") == 0) ? PREC_F64 : PREC_F32;
     hipError_t se = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
     if (se != hipSuccess) return fail(SLM_ERR_HIP, "stream creation failed: %s", hipGetErrorString(se));
@@ -306,6 +321,7 @@ int plan_create_on(int device, int algo, int batch, int height, int width, int t
         RC(dev_alloc(&s.field0, n * sizeof(float2)));
         RC(dev_alloc(&s.lr, (size_t)max_loops * sizeof(float)));
     }
+    if (algo == SLM_ALGO_GSW) RC(dev_alloc(&s.weights0, n * sizeof(float)));
     RC(dev_alloc(&s.tgt, n * (tgt_type == SLM_TGT_U8 ? 1 : 4)));
     if (has_ain) RC(dev_alloc(&s.ain, (size_t)s.holo * sizeof(float)));
     RC(dev_alloc(&s.phase_out, n * sizeof(float)));
@@ -511,6 +527,9 @@ int slm_plan_set_target(slm_plan* p, const void* tgt) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s.stream));
     p->target_set = true;
+    // host-set weights were validated on the previous target's support
+    s.weights_set = false;
+    p->weights_fresh = false;
     return 0;
 }
 
@@ -564,7 +583,7 @@ int slm_plan_set_ain(slm_plan* p, const float* ain) {
 int slm_plan_set_phase(slm_plan* p, const float* phase) {
     if (!p) return fail(SLM_ERR_ARG, "null plan");
     PlanState& s = p->s;
-    if (s.algo != SLM_ALGO_GS) return fail(SLM_ERR_STATE, "initial phase applies to GS plans");
+    if (!gs_like(s.algo)) return fail(SLM_ERR_STATE, "initial phase applies to GS plans");
     HIP_TRY(hipSetDevice(s.device));
     if (!phase) {
         p->phase_set = false;
@@ -595,6 +614,54 @@ int slm_plan_set_field(slm_plan* p, const float* field) {
     return 0;
 }
 
+int slm_plan_set_feedback(slm_plan* p, float feedback) {
+    if (!p) return fail(SLM_ERR_ARG, "null plan");
+    if (!(feedback >= 0.f) || !std::isfinite(feedback))
+        return fail(SLM_ERR_ARG, "feedback exponent %g is not a finite number >= 0", (double)feedback);
+    if (p->s.algo != SLM_ALGO_GSW) return fail(SLM_ERR_STATE, "the feedback exponent applies to weighted-GS plans");
+    p->s.feedback = feedback;
+    return 0;
+}
+
+int slm_plan_set_weights(slm_plan* p, const float* w) {
+    if (!p) return fail(SLM_ERR_ARG, "null plan");
+    PlanState& s = p->s;
+    if (s.algo != SLM_ALGO_GSW) return fail(SLM_ERR_STATE, "weights apply to weighted-GS plans");
+    Engine* e = nullptr;
+    RC(engine_of(p, &e));
+    HIP_TRY(hipSetDevice(s.device));
+    if (!w) {
+        s.weights_set = false;
+        p->weights_fresh = true;
+        return 0;
+    }
+    if (!p->target_set) return fail(SLM_ERR_STATE, "set the target first: weights are checked on its support");
+    HIP_TRY(hipStreamSynchronize(s.stream));  // the staging buffer is scratch of a queued run
+    s.weights_set = false;
+    bool bad = false;
+    RC(e->land_weights(s, w, &bad));
+    if (bad) return fail(SLM_ERR_ARG, "weights on the support (T > 0) must be positive and finite");
+    s.weights_set = true;
+    p->weights_fresh = true;
+    return 0;
+}
+
+int slm_plan_read_weights(slm_plan* p, float* w) {
+    if (!p || !w) return fail(SLM_ERR_ARG, "null argument");
+    PlanState& s = p->s;
+    if (s.algo != SLM_ALGO_GSW) return fail(SLM_ERR_STATE, "weights are the state of weighted-GS plans");
+    Engine* e = nullptr;
+    RC(engine_of(p, &e));
+    RC(slm_plan_sync(p));
+    const bool fresh = p->weights_fresh || !p->ran;
+    if (fresh && !s.weights_set) {  // ones
+        std::fill(w, w + (size_t)s.B * s.holo, 1.f);
+        return 0;
+    }
+    if (!p->target_set) return fail(SLM_ERR_STATE, "target not set");
+    return e->read_weights(s, fresh, w);
+}
+
 int slm_plan_set_lr(slm_plan* p, const float* lr) {
     if (!p || !lr) return fail(SLM_ERR_ARG, "null argument");
     PlanState& s = p->s;
@@ -611,6 +678,7 @@ int slm_plan_run(slm_plan* p, int loops, double tol, int checked, float wa) {
     RC(engine_of(p, &e));
     PlanState& s = p->s;
     p->field_fresh = false;  // replays skip enqueue_run
+    p->weights_fresh = false;
     p->last_loops = loops;
     p->last_tol = tol;
     p->last_checked = checked;
@@ -624,8 +692,8 @@ int slm_plan_run(slm_plan* p, int loops, double tol, int checked, float wa) {
         e->queued(s, checked);
         return 0;
     }
-    const int state = (p->phase_set ? 1 : 0) | (p->field_set ? 2 : 0);
-    if (!p->gexec || p->g_state != state || p->g_loops != loops || p->g_tol != tol || p->g_checked != checked || p->g_wa != wa) {
+    const int state = (p->phase_set ? 1 : 0) | (p->field_set ? 2 : 0) | (s.weights_set ? 4 : 0);
+    if (!p->gexec || p->g_state != state || p->g_fb != s.feedback || p->g_loops != loops || p->g_tol != tol || p->g_checked != checked || p->g_wa != wa) {
         HIP_TRY(hipSetDevice(s.device));
         RC(drop_graph(p));
         HIP_TRY(hipStreamBeginCapture(s.stream, hipStreamCaptureModeThreadLocal));
@@ -644,6 +712,7 @@ int slm_plan_run(slm_plan* p, int loops, double tol, int checked, float wa) {
         p->g_tol = tol;
         p->g_checked = checked;
         p->g_wa = wa;
+        p->g_fb = s.feedback;
         p->g_state = state;
     }
     HIP_TRY(hipSetDevice(s.device));
@@ -823,6 +892,23 @@ int slm_gs(const void* tgt, int tgt_type, const float* ain, int batch, int heigh
     return rc;
 }
 
+int slm_gsw(const void* tgt, int tgt_type, const float* ain, int batch, int height, int width, int max_loops,
+            double tol, const float* init_phase, float* out_phase, float* out_expected, double* out_stats,
+            int* out_iters, float feedback, const float* init_weights, float* out_weights) {
+    slm_plan* p = nullptr;
+    RC(slm_plan_create(SLM_ALGO_GSW, batch, height, width, tgt_type, ain != nullptr, max_loops, &p));
+    int rc = slm_plan_set_target(p, tgt);
+    if (!rc) rc = slm_plan_set_feedback(p, feedback);
+    if (!rc && ain) rc = slm_plan_set_ain(p, ain);
+    if (!rc && init_phase) rc = slm_plan_set_phase(p, init_phase);
+    if (!rc && init_weights) rc = slm_plan_set_weights(p, init_weights);
+    if (!rc) rc = slm_plan_run(p, max_loops, tol, tol > 0.0 ? 1 : 0, 0.f);
+    if (!rc) rc = slm_plan_read(p, out_phase, out_expected, out_stats, out_iters);
+    if (!rc && out_weights) rc = slm_plan_read_weights(p, out_weights);
+    free_plan(p);
+    return rc;
+}
+
 int slm_gd(const void* tgt, int tgt_type, const float* ain, int batch, int height, int width, int max_loops,
            double tol, const float* init_field, const float* lr, float wa, float* out_phase, float* out_expected,
            double* out_stats, int* out_iters) {
@@ -848,9 +934,30 @@ int slm_gs_multi_timing(int max_shards, double* wall_ms, double* run_ms) {
     return n;
 }
 
+static int gs_multi_run(int algo, float feedback, int n_gpus, const int* devices, const void* tgt, int tgt_type,
+                        const float* ain, int batch, int height, int width, int max_loops, double tol,
+                        const float* init_phase, float* out_phase, float* out_expected, double* out_stats,
+                        int* out_iters);
+
 int slm_gs_multi(int n_gpus, const int* devices, const void* tgt, int tgt_type, const float* ain, int batch,
                  int height, int width, int max_loops, double tol, const float* init_phase, float* out_phase,
                  float* out_expected, double* out_stats, int* out_iters) {
+    return gs_multi_run(SLM_ALGO_GS, 0.f, n_gpus, devices, tgt, tgt_type, ain, batch, height, width, max_loops, tol,
+                        init_phase, out_phase, out_expected, out_stats, out_iters);
+}
+
+int slm_gsw_multi(int n_gpus, const int* devices, const void* tgt, int tgt_type, const float* ain, int batch,
+                  int height, int width, int max_loops, double tol, const float* init_phase, float* out_phase,
+                  float* out_expected, double* out_stats, int* out_iters, float feedback) {
+    return gs_multi_run(SLM_ALGO_GSW, feedback, n_gpus, devices, tgt, tgt_type, ain, batch, height, width, max_loops,
+                        tol, init_phase, out_phase, out_expected, out_stats, out_iters);
+}
+
+// slm_gs_multi / slm_gsw_multi: shard r of the batch on devices[r], one host thread and plan each
+static int gs_multi_run(int algo, float feedback, int n_gpus, const int* devices, const void* tgt, int tgt_type,
+                        const float* ain, int batch, int height, int width, int max_loops, double tol,
+                        const float* init_phase, float* out_phase, float* out_expected, double* out_stats,
+                        int* out_iters) {
     if (n_gpus < 1) return fail(SLM_ERR_ARG, "n_gpus must be >= 1");
     if (!tgt || batch < 1) return fail(SLM_ERR_ARG, "need a target batch");
     int ndev = 0;
@@ -879,8 +986,8 @@ int slm_gs_multi(int n_gpus, const int* devices, const void* tgt, int tgt_type, 
         const auto t0 = clk::now();
         const long long h0 = off[r];
         slm_plan* p = nullptr;
-        int rc = plan_create_on(dev[r], SLM_ALGO_GS, counts[r], height, width, tgt_type, ain != nullptr, max_loops,
-                                &p);
+        int rc = plan_create_on(dev[r], algo, counts[r], height, width, tgt_type, ain != nullptr, max_loops, &p);
+        if (!rc && algo == SLM_ALGO_GSW) rc = slm_plan_set_feedback(p, feedback);
         if (!rc) rc = slm_plan_set_target(p, static_cast<const char*>(tgt) + (size_t)h0 * holo * tb);
         if (!rc && ain) rc = slm_plan_set_ain(p, ain);
         if (!rc && init_phase) rc = slm_plan_set_phase(p, init_phase + h0 * holo);

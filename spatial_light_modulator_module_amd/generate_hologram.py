@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from . import constants as c
-from .algorithms import gerchberg_saxton, gradient_descent
+from .algorithms import gerchberg_saxton, gradient_descent, weighted_gerchberg_saxton
 
 
 def main(args):
@@ -99,7 +99,8 @@ def prepare_target(img_name, args):
 
 def make_hologram(args):
     """src/generate_hologram.py:70-79."""
-    algorithm = gerchberg_saxton if args.algorithm == "gerchberg_saxton" else gradient_descent
+    algorithm = {"gerchberg_saxton": gerchberg_saxton,
+                 "weighted_gerchberg_saxton": weighted_gerchberg_saxton}.get(args.algorithm, gradient_descent)
     target = prepare_target(args.img_name, args)
     if args.gif:
         add_gif_dirs(args)
@@ -253,7 +254,10 @@ def build_parser():
     p.add_argument("-q", "--quarterize", action="store_true", help="paste the image into one quadrant")
     p.add_argument("-i", "--invert", action="store_true", help="invert colors of the target image")
     p.add_argument("-alg", "--algorithm", default="gerchberg_saxton",
-                   choices=["gerchberg_saxton", "gradient_descent"], help="algorithm")
+                   choices=["gerchberg_saxton", "gradient_descent", "weighted_gerchberg_saxton"],
+                   help="algorithm (weighted_gerchberg_saxton: GS with trap-intensity feedback)")
+    p.add_argument("--feedback", default=1.0, type=float, metavar="FLOAT",
+                   help="weight feedback exponent of weighted_gerchberg_saxton")
     p.add_argument("-tol", "--tolerance", default=0, metavar="FLOAT", type=float,
                    help="algorithm stops when error descends under tolerance")
     p.add_argument("-l", "--max_loops", default=42, metavar="INTEGER", type=int,

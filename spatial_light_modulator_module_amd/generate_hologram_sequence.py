@@ -25,7 +25,7 @@ import numpy as np
 from . import parallel
 from . import _lib
 from .algorithms import (_check_shape, _print_loops, expected_from, hologram_from, incoming_amplitude, run_gs,
-                         run_gs_multi)
+                         run_gs_multi, run_gsw)
 
 SEQ_BATCH = int(os.environ.get("SLM_SEQ_BATCH", "64"))  # frames per GPU launch batch
 
@@ -84,8 +84,13 @@ def generate_hologram_sequence(args, rank=None, nranks=None):
         ain = incoming_amplitude(args, stack.shape[1:])
         if not (args.max_loops > 0 and (args.tolerance + 1) > args.tolerance):
             raise UnboundLocalError("local variable 'expected_outcome' referenced before assignment")
+        # -alg weighted_gerchberg_saxton (no reference counterpart): the same batches, weighted GS
+        feedback = (float(getattr(args, "feedback", 1.0))
+                    if getattr(args, "algorithm", "gerchberg_saxton") == "weighted_gerchberg_saxton" else None)
         if devices:
-            phase, e, errs, norm, emax = run_gs_multi(stack, args.max_loops, devices, args.tolerance, ain)
+            phase, e, errs, norm, emax = run_gs_multi(stack, args.max_loops, devices, args.tolerance, ain, feedback)
+        elif feedback is not None:
+            phase, e, errs, norm, emax = run_gsw(stack, args.max_loops, feedback, args.tolerance, ain)
         else:
             phase, e, errs, norm, emax = run_gs(stack, args.max_loops, args.tolerance, ain)
         for k, i in enumerate(idx):
@@ -124,6 +129,11 @@ def build_parser():
     p.add_argument("-loops", "--max_loops", metavar="INT", default=5, type=int,
                    help="algorithm performs no more than max_loops loops")
     p.add_argument("-p", "--preview", action="store_true", help="also write expected images")
+    p.add_argument("-alg", "--algorithm", default="gerchberg_saxton",
+                   choices=["gerchberg_saxton", "weighted_gerchberg_saxton"],
+                   help="algorithm (weighted_gerchberg_saxton evens out the trap intensities)")
+    p.add_argument("--feedback", metavar="FLOAT", default=1.0, type=float,
+                   help="weight feedback exponent of weighted_gerchberg_saxton")
     return p
 
 
