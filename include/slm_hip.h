@@ -109,6 +109,9 @@ int slm_plan_set_lr(slm_plan* plan, const float* lr);             /* GD learning
  * target made uniform is a ~1e-4 remainder of those sums). Only angle(A) and E leave the loop, so g is defined up to a
  * positive factor per hologram: the device keeps it near mean 1 over the support
  * with the previous iteration's sum and clamps it to [2^-40, 2^40] of that scale.
+ * On trap targets the iteration is contracting for the exponents tested up to
+ * p = 1.5 (a small change of the start shrinks) and is not at p = 2, where it
+ * grows: runs with p >= 2 stay finite but are not reproducible to rounding.
  * Plans of the fused engine only: both sides one of 64 ... 4096 (powers of two)
  * or 768; other shapes and $SLM_ENGINE=float64 get SLM_ERR_UNSUPPORTED from
  * slm_plan_create. slm_plan_set_phase warm-starts such a plan as a GS plan.

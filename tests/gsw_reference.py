@@ -20,10 +20,23 @@ def uniformity(e, t):
     return float(r.std() / r.mean())
 
 
-def gsw_reference(target, loops, feedback=1.0, initial_phase=None, initial_weights=None):
+def incoming_gauss(h, w):
+    """The incoming amplitude the a_in tests share: a wide Gaussian on a 0.2
+    pedestal, float32 (0.2 + exp(-(((y - H/2) / 0.35 H)^2 + ((x - W/2) / 0.35 W)^2)))."""
+    y = (np.arange(h)[:, None] - h / 2) / (0.35 * h)
+    x = (np.arange(w)[None, :] - w / 2) / (0.35 * w)
+    return (0.2 + np.exp(-(y ** 2 + x ** 2))).astype(np.float32)
+
+
+def gsw_reference(target, loops, feedback=1.0, initial_phase=None, initial_weights=None, ain=None, factors=None):
     """(phase, E, error_evolution, g): g normalised to mean 1 over the support,
     1 off it. feedback = 0 is plain GS. The amplitude follows numpy's dtype
-    rule as GS does: float16 sqrt for uint8 targets, float32 for float32."""
+    rule as GS does: float16 sqrt for uint8 targets, float32 for float32.
+    ain: the incoming amplitude a_in [H][W] of B = a_in exp(i angle(A)); None is
+    uniform and computes what this function computed before it took a_in, bit
+    for bit. factors: a list that receives (min, max) of every iteration's
+    update factor (a_T / |C|)^feedback (an observer; the kernels clamp it to
+    [2^-64, 2^64] and the tests assert that the clamp is idle)."""
     t = np.asarray(target)
     a_t = np.sqrt(t).astype(np.float64)
     sup = t > 0
@@ -33,10 +46,14 @@ def gsw_reference(target, loops, feedback=1.0, initial_phase=None, initial_weigh
     a = np.fft.ifft2(a_t) if initial_phase is None else np.exp(1j * np.asarray(initial_phase, np.float64))
     errs = []
     for _ in range(loops):
-        c = np.fft.fft2(np.exp(1j * np.angle(a)))
+        b = np.exp(1j * np.angle(a))
+        c = np.fft.fft2(b if ain is None else np.asarray(ain, np.float64) * b)
         amp = np.abs(c)
         upd = sup & (amp > 0)
-        g[upd] *= (a_t[upd] / amp[upd]) ** feedback
+        f = (a_t[upd] / amp[upd]) ** feedback
+        if factors is not None:
+            factors.append((float(f.min()), float(f.max())))
+        g[upd] *= f
         g[sup] /= g[sup].mean()
         a = np.fft.ifft2(a_t * g * np.exp(1j * np.angle(c)))
         e = amp ** 2

@@ -112,7 +112,8 @@ def _case_run(gpu, label, shape, nt, dtype, feedback, warm, more):
 
 
 def _batch_run(gpu):
-    """eight different 256 x 256 targets in one plan (the wide plans)"""
+    """eight different 256 x 256 targets in one plan (512 waves: still the narrow
+    plans, keys 8 / 8; the wide keys run in test_gpu_gsw_variants.py)"""
     return _parity_run(gpu, "8x256x256", [traps(256, 256, 24, seed, True) for seed in range(8)], 1.0, 30, 20)
 
 
