@@ -17,6 +17,9 @@
  *   slm_gsw / slm_plan_* with SLM_ALGO_GSW -> no reference counterpart: GS with Di Leonardo's
  *                                            per-pixel weight feedback, an addition next to
  *                                            the drop-in (see "weighted GS" below).
+ *   slm_spots_*                           -> no reference counterpart: weighted GS on a list
+ *                                            of traps (fractional positions, defocus, any
+ *                                            panel shape; see "trap lists" below).
  *   slm_comm_* / slm_plan_gather_phase    -> no reference counterpart: the batch
  *                                            loop of src/generate_hologram_sequence.py:19-31
  *                                            sharded over GPUs, phases gathered over RCCL.
@@ -307,6 +310,79 @@ int slm_trap_frames(int batch, int height, int width, const int* ys, const int* 
                     double ct2pi, int rule, double* phase_out, unsigned char* frame_out);
 int slm_quantize(const void* src, int src_type, const double* mask, int batch, int height, int width, double ct2pi,
                  int rule, unsigned char* out);
+
+/* ---- trap lists: no reference counterpart --------------------------------
+ * Weighted GS in its spot form (Di Leonardo et al. 2007): the field is
+ * evaluated at the M traps only, with no transform, so every panel shape runs
+ * (sides 2 ... 4096, 1 <= M <= 1024). Per hologram of H x W pixels (row k,
+ * column l), with a = a_in or ones, traps at (y_m, x_m) in far-field pixel
+ * units (real numbers, any sign), a defocus z_m in radians per pixel^2, target
+ * intensities I_m > 0, a_T,m = sqrt(I_m) and the feedback exponent p >= 0:
+ *     D_m(k,l) = 2 pi (k y_m / H + l x_m / W) + z_m ((k - H/2)^2 + (l - W/2)^2)
+ *     start:   w = 1 (or the caller's); phi = the caller's phase, or
+ *              angle(sum_m a_T,m exp(i (D_m + theta_m))), theta_m = 2 pi frac(m 0.6180339887498949)
+ *     each iteration:
+ *         V_m = sum_kl a(k,l) exp(i (phi(k,l) - D_m(k,l)))
+ *         where |V_m| > 0:  w_m *= (a_T,m / |V_m|)^p, the factor clamped to [2^-64, 2^64];
+ *         w /= mean(w)   (over all M traps, current each iteration)
+ *         phi = angle(sum_m a_T,m w_m (V_m / |V_m|) exp(i D_m))          (angle(0) = 0)
+ *         statistics from V, before the update, with r_m = (|V_m|^2 / I_m) / mean_m(|V_m|^2 / I_m):
+ *             (efficiency sum_m |V_m|^2 / (H W sum a^2), uniformity std(r), min r, max r)
+ * For integer (y, x) and z = 0, V_m is fft2(a exp(i phi))[y][x]; for M = 1 the
+ * hologram is slm_trap_frames' (update_hologram); p = 0 is unweighted spot GS.
+ * The state is the unit field exp(i phi), complex64; both sums run as float32
+ * matrix products on the matrix cores (v_mfma_f32_32x32x2_f32), the fold over
+ * rows, the statistics and the weights in float64. Results are bitwise
+ * reproducible and do not depend on the batch a hologram sits in.
+ *
+ * slm_spots_create: `batch` holograms of height x width with up to max_traps
+ *   traps each; has_ain != 0 requires slm_spots_set_ain before a run.
+ * slm_spots_set_traps: ys, xs, zs (NULL = 0), intensity (NULL = 1), each
+ *   [batch][n_traps]; builds the phase tables on the device (float64, rounded to
+ *   complex64) and returns the weights to ones. A non-finite coordinate, or an
+ *   intensity that is not positive and finite, gives SLM_ERR_ARG.
+ * slm_spots_set_ain: [height][width] sqrt(incoming intensity), as slm_plan_set_ain.
+ * slm_spots_set_phase: start phase [batch][h][w] float32, NULL = the start above.
+ * slm_spots_set_weights: start weights [batch][n_traps], NULL = ones; call after
+ *   slm_spots_set_traps; an entry that is not positive and finite gives SLM_ERR_ARG.
+ * slm_spots_set_feedback: p (default 1); negative or non-finite gives SLM_ERR_ARG.
+ * The start phase and weights live in buffers that runs read and never write:
+ * every run starts from them again.
+ * slm_spots_run: `loops` (1 ... max_loops) iterations, enqueued on the handle's stream.
+ * slm_spots_run_timed: the same, every launch timed with HIP events;
+ *   us_per_class[SLM_SPOTS_NUM_KERNEL_CLASSES] receives microseconds per class.
+ * slm_spots_read: phase [batch][h][w] float32; fields [batch][n_traps][2] = V of
+ *   the last iteration; stats [batch][loops][4] (loops of the last run);
+ *   weights [batch][n_traps] (mean 1). Any pointer may be NULL; SLM_ERR_STATE
+ *   before a run.
+ * slm_spots_info: info[0] = Mp (the trap count padded to the matrix-core tile, 32),
+ *   info[1] = partial sums per hologram and trap the fields kernel writes,
+ *   info[2] = columns per such partial (each covers 128 rows), info[3] = waves
+ *   per workgroup of the two product kernels (info holds 4 ints).
+ * slm_spots_fields / slm_spots_superpose: one-shot test entries for the two
+ *   products alone: V [batch][n_traps][2] of exp(i phase) (times a_in), and
+ *   angle(sum_m c_m exp(i D_m)) for complex c [batch][n_traps][2].           */
+#define SLM_SPOTS_KERNEL_FIELDS 0    /* spot_fields_kernel: V partials */
+#define SLM_SPOTS_KERNEL_UPDATE 1    /* spot_update_kernel: fold, statistics, weights */
+#define SLM_SPOTS_KERNEL_SUPERPOSE 2 /* spot_superpose_kernel: the next unit field (and the phase) */
+#define SLM_SPOTS_NUM_KERNEL_CLASSES 3
+typedef struct slm_spots slm_spots;
+int slm_spots_create(int batch, int height, int width, int max_traps, int has_ain, int max_loops, slm_spots** out);
+int slm_spots_destroy(slm_spots* sp);
+int slm_spots_set_traps(slm_spots* sp, int n_traps, const double* ys, const double* xs, const double* zs,
+                        const float* intensity);
+int slm_spots_set_ain(slm_spots* sp, const float* ain);
+int slm_spots_set_phase(slm_spots* sp, const float* phase);
+int slm_spots_set_weights(slm_spots* sp, const float* weights);
+int slm_spots_set_feedback(slm_spots* sp, float feedback);
+int slm_spots_run(slm_spots* sp, int loops);
+int slm_spots_run_timed(slm_spots* sp, int loops, double* us_per_class);
+int slm_spots_read(slm_spots* sp, float* phase, double* fields, double* stats, float* weights);
+int slm_spots_info(slm_spots* sp, int* info);
+int slm_spots_fields(int batch, int height, int width, int n_traps, const double* ys, const double* xs,
+                     const double* zs, const float* ain, const float* phase, double* fields_out);
+int slm_spots_superpose(int batch, int height, int width, int n_traps, const double* ys, const double* xs,
+                        const double* zs, const double* c_re_im, float* phase_out);
 
 /* ---- CLI post-processing ------------------------------
  * slm_transform_hologram -> transform_hologram(hologram, args)

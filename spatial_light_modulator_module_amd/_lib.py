@@ -120,7 +120,27 @@ _SIGNATURES = [
     ("slm_fft2_intensity", _c_int, [_vp, _c_int, _c_int, _c_int, _vp]),
     ("slm_fft2_c128", _c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int]),
     ("slm_release_caches", _c_int, []),
+    ("slm_spots_create", _c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _P(_vp)]),
+    ("slm_spots_destroy", _c_int, [_vp]),
+    ("slm_spots_set_traps", _c_int, [_vp, _c_int, _vp, _vp, _vp, _vp]),
+    ("slm_spots_set_ain", _c_int, [_vp, _vp]),
+    ("slm_spots_set_phase", _c_int, [_vp, _vp]),
+    ("slm_spots_set_weights", _c_int, [_vp, _vp]),
+    ("slm_spots_set_feedback", _c_int, [_vp, _c_float]),
+    ("slm_spots_run", _c_int, [_vp, _c_int]),
+    ("slm_spots_run_timed", _c_int, [_vp, _c_int, _vp]),
+    ("slm_spots_read", _c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("slm_spots_info", _c_int, [_vp, _vp]),
+    ("slm_spots_fields", _c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("slm_spots_superpose", _c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
 ]
+
+SPOTS_KERNEL_FIELDS = 0
+SPOTS_KERNEL_UPDATE = 1
+SPOTS_KERNEL_SUPERPOSE = 2
+SPOTS_NUM_KERNEL_CLASSES = 3
+SPOTS_KERNEL_CLASS_NAMES = ("fields", "update", "superpose")
+SPOTS_MAX_TRAPS = 1024
 
 TRANSFORM_DEFLECT = 1
 TRANSFORM_LENS = 2
@@ -442,6 +462,144 @@ class Plan:
         it = np.empty(total, np.int32) if want else None
         check(self._lib.slm_plan_gather_stats(self.handle, ptr(c), root, ptr(st), ptr(it)), "slm_plan_gather_stats")
         return st, it
+
+
+def _trap_arrays(batch, n_traps, ys, xs, zs, intensity):
+    """Trap coordinates as the C-contiguous [batch][n_traps] arrays slm_spots_* take."""
+    y = np.ascontiguousarray(ys, dtype=np.float64).reshape(batch, n_traps)
+    x = np.ascontiguousarray(xs, dtype=np.float64).reshape(batch, n_traps)
+    z = None if zs is None else np.ascontiguousarray(zs, dtype=np.float64).reshape(batch, n_traps)
+    i = None if intensity is None else np.ascontiguousarray(intensity, dtype=np.float32).reshape(batch, n_traps)
+    return y, x, z, i
+
+
+class Spots:
+    """Device-resident weighted GS on trap lists (slm_spots_* in
+    include/slm_hip.h): `batch` holograms of height x width with up to
+    max_traps traps each, any panel shape."""
+
+    def __init__(self, batch: int, height: int, width: int, max_traps: int, has_ain: bool = False,
+                 max_loops: int = 30):
+        init()
+        self._lib = load()
+        h = ctypes.c_void_p()
+        check(self._lib.slm_spots_create(int(batch), int(height), int(width), int(max_traps), int(bool(has_ain)),
+                                         int(max_loops), ctypes.byref(h)), "slm_spots_create")
+        self.handle = h
+        self.batch, self.height, self.width = int(batch), int(height), int(width)
+        self.max_traps, self.has_ain, self.max_loops = int(max_traps), bool(has_ain), int(max_loops)
+        self.n_traps = 0
+        self.loops = 0
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self._lib.slm_spots_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover - best effort
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def shape(self):
+        return (self.batch, self.height, self.width)
+
+    def set_traps(self, ys, xs, zs=None, intensity=None) -> None:
+        """Trap lists [batch][n_traps]: positions in far-field pixels, defocus in
+        radians per pixel^2 (None = 0), target intensities (None = 1). Returns
+        the weights to ones."""
+        n = np.asarray(ys).size // self.batch
+        if n * self.batch != np.asarray(ys).size:
+            raise ValueError(f"{np.asarray(ys).size} trap rows do not divide into a batch of {self.batch}")
+        y, x, z, i = _trap_arrays(self.batch, n, ys, xs, zs, intensity) if n else (np.zeros(0),) * 2 + (None,) * 2
+        check(self._lib.slm_spots_set_traps(self.handle, n, ptr(y), ptr(x), ptr(z), ptr(i)), "slm_spots_set_traps")
+        self.n_traps = n
+
+    def set_ain(self, ain: np.ndarray) -> None:
+        a = np.ascontiguousarray(ain, dtype=np.float32).reshape(self.height, self.width)
+        check(self._lib.slm_spots_set_ain(self.handle, ptr(a)), "slm_spots_set_ain")
+
+    def set_phase(self, phase: np.ndarray | None) -> None:
+        a = None if phase is None else np.ascontiguousarray(phase, dtype=np.float32).reshape(self.shape)
+        check(self._lib.slm_spots_set_phase(self.handle, ptr(a)), "slm_spots_set_phase")
+
+    def set_weights(self, weights: np.ndarray | None) -> None:
+        a = None
+        if weights is not None:
+            a = np.ascontiguousarray(weights, dtype=np.float32).reshape(self.batch, max(self.n_traps, 1))
+        check(self._lib.slm_spots_set_weights(self.handle, ptr(a)), "slm_spots_set_weights")
+
+    def set_feedback(self, feedback: float) -> None:
+        check(self._lib.slm_spots_set_feedback(self.handle, float(feedback)), "slm_spots_set_feedback")
+
+    def run(self, loops: int) -> None:
+        check(self._lib.slm_spots_run(self.handle, int(loops)), "slm_spots_run")
+        self.loops = int(loops)
+
+    def run_timed(self, loops: int) -> np.ndarray:
+        """As run; returns microseconds per kernel class (SPOTS_KERNEL_*), HIP events."""
+        us = np.zeros(SPOTS_NUM_KERNEL_CLASSES, np.float64)
+        check(self._lib.slm_spots_run_timed(self.handle, int(loops), ptr(us)), "slm_spots_run_timed")
+        self.loops = int(loops)
+        return us
+
+    def read(self, phase=True, fields=True, stats=True, weights=True):
+        """(phase float32 [B][H][W], V complex128 [B][M] of the last iteration,
+        stats [B][loops][4] = (efficiency, uniformity, min r, max r), weights
+        float32 [B][M]); None where not asked for."""
+        n = max(self.n_traps, 1)
+        out_phase = np.empty(self.shape, np.float32) if phase else None
+        out_v = np.empty((self.batch, n), np.complex128) if fields else None
+        out_stats = np.empty((self.batch, max(self.loops, 1), 4), np.float64) if stats else None
+        out_w = np.empty((self.batch, n), np.float32) if weights else None
+        check(self._lib.slm_spots_read(self.handle, ptr(out_phase), None if out_v is None else out_v.ctypes.data,
+                                       ptr(out_stats), ptr(out_w)), "slm_spots_read")
+        return out_phase, out_v, out_stats, out_w
+
+    def info(self) -> dict:
+        a = np.zeros(4, np.int32)
+        check(self._lib.slm_spots_info(self.handle, ptr(a)), "slm_spots_info")
+        return {"padded_traps": int(a[0]), "partials": int(a[1]), "cols_per_partial": int(a[2]),
+                "waves_per_workgroup": int(a[3])}
+
+
+def spots_fields(phase, ys, xs, zs=None, ain=None) -> np.ndarray:
+    """slm_spots_fields (test entry): V [B][M] complex128 of exp(i phase)
+    [B][H][W] (times ain [H][W]) at the traps ys, xs, zs [B][M]."""
+    ph = np.ascontiguousarray(phase, dtype=np.float32)
+    ph = ph[None] if ph.ndim == 2 else ph
+    b, h, w = ph.shape
+    n = np.asarray(ys).size // b
+    y, x, z, _ = _trap_arrays(b, n, ys, xs, zs, None)
+    a = None if ain is None else np.ascontiguousarray(ain, dtype=np.float32).reshape(h, w)
+    out = np.empty((b, n), np.complex128)
+    init()
+    check(load().slm_spots_fields(b, h, w, n, ptr(y), ptr(x), ptr(z), ptr(a), ptr(ph), out.ctypes.data),
+          "slm_spots_fields")
+    return out
+
+
+def spots_superpose(shape, c, ys, xs, zs=None) -> np.ndarray:
+    """slm_spots_superpose (test entry): angle(sum_m c_m exp(i D_m)), float32
+    [B][H][W], for complex c [B][M] and traps ys, xs, zs [B][M]."""
+    h, w = shape
+    cc = np.ascontiguousarray(c, dtype=np.complex128)
+    cc = cc[None] if cc.ndim == 1 else cc
+    b, n = cc.shape
+    y, x, z, _ = _trap_arrays(b, n, ys, xs, zs, None)
+    out = np.empty((b, h, w), np.float32)
+    init()
+    check(load().slm_spots_superpose(b, h, w, n, ptr(y), ptr(x), ptr(z), cc.ctypes.data, ptr(out)),
+          "slm_spots_superpose")
+    return out
 
 
 def fft2(x: np.ndarray, inverse: bool = False) -> np.ndarray:

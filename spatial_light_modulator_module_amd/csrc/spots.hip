@@ -1,0 +1,904 @@
+// Spot-based weighted Gerchberg-Saxton for trap lists (include/slm_hip.h,
+// "trap lists"; DESIGN.md section 3, "Trap lists"). No reference counterpart.
+//
+// The field is evaluated at the M traps only, so there is no transform and no
+// radix plan: every panel shape runs. The trap phase is separable,
+//     D_m(k, l) = fy_m(k) + fx_m(l),
+//     fy_m(k) = 2 pi frac(k y_m / H) + z_m (k - H/2)^2   (fx likewise on l, x_m, W),
+// so with the tables Py[k][m] = exp(i fy_m(k)) and Px[l][m] = exp(i fx_m(l)) one
+// iteration is two complex matrix products with the trap count as a dimension:
+//     V_m     = sum_k conj(Py[k][m]) sum_l (a U)[k][l] conj(Px[l][m])     spot_fields_kernel
+//     weights, statistics, c_m = a_T,m w_m V_m / |V_m|  (float64)        spot_update_kernel
+//     S[k][l] = sum_m (Py[k][m] c_m) Px[l][m];  U = S / |S|              spot_superpose_kernel
+// The state is the unit field U = exp(i phi), complex64: the loop never takes
+// an angle; the float32 phase is formed by the last superposition.
+//
+// Both products run on v_mfma_f32_32x32x2_f32 (exact f32: a k-ordered fmaf
+// chain). A complex product is a real one with K doubled. The K = 2 of one
+// instruction is spread over the two lane halves, so lane half h carries summed
+// index 2 j + h and one MFMA each takes the real and the imaginary parts:
+//     re += a.x * b.x;  im += a.x * b.y;  re += a.y * (-b.y);  im += a.y * b.x
+// (for the fields product b is conj(Px), which moves the sign). Four MFMAs per
+// step and 32 x 32 output tile = 8 FLOP per pixel and trap.
+//
+// Tables, built at slm_spots_set_traps in float64 and rounded to complex64,
+// are kept in two layouts so that every operand is read along its fast index:
+//   row layout   [n][Mp]  (Py, Px): lanes run over traps; the fields product's
+//                B operand (256 B per lane half per step) and its epilogue
+//   trap layout  [m][n]   (PyT, PxT): lanes run over pixels; both operands of
+//                the superposition (256 B per lane half per step)
+// Mp is M padded with zero columns to a multiple of 32.
+// The fields product's A operand is the field itself, [k][l] with l summed:
+// lanes run over rows there, so each 32 x 32 tile goes through LDS, written as
+// whole 256 B row segments and read back as 8 B per lane with a row stride of
+// 66 floats: lane (i, h) reads banks 2 i + 2 h (+1) mod 64 of step j's 4 j
+// offset, all 64 banks once per 32 lanes.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "runtime.hpp"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr double kTwoPi = 6.283185307179586;
+constexpr double kGolden = 0.6180339887498949;
+constexpr int kTile = 32;         // MFMA tile side
+constexpr int kLdsStride = 66;    // floats per staged field row (64 + 2: conflict-free 8 B reads)
+constexpr int kUpdThreads = 1024; // spot_update_kernel: one trap per thread after the fold
+constexpr int kMaxTraps = 1024;
+constexpr int kMinSide = 2, kMaxSide = 4096;
+constexpr int kWaves = 4;           // waves per workgroup of the two product kernels
+constexpr int kFieldsThreads = 64 * kWaves;
+constexpr int kTargetWaves = 4096;  // fields grid: split columns until this many waves per hologram
+
+// row of accumulator register r of a 32x32 MFMA result in lane half h (the column is lane & 31)
+__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+__device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
+}
+
+// ---- tables ---------------------------------------------------------------
+struct TableParams {
+    const double* pos;  // [B][M] trap coordinate along this axis
+    const double* z;    // [B][M] defocus
+    float2* out;        // [B][N][Mp] or (transposed) [B][Mp][N]
+    int N, M, Mp, transposed;
+};
+
+__global__ void __launch_bounds__(256) spot_table_kernel(TableParams p) {
+    const long long n_el = (long long)p.N * p.Mp;
+    const int b = blockIdx.y;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n_el; i += (long long)gridDim.x * 256) {
+        int n, m;
+        if (p.transposed) {
+            m = (int)(i / p.N);
+            n = (int)(i - (long long)m * p.N);
+        } else {
+            n = (int)(i / p.Mp);
+            m = (int)(i - (long long)n * p.Mp);
+        }
+        float2 v = make_float2(0.0f, 0.0f);
+        if (m < p.M) {
+            const double pos = p.pos[(size_t)b * p.M + m], z = p.z[(size_t)b * p.M + m];
+            double t = (double)n * pos / (double)p.N;
+            t -= floor(t);  // the argument of the sine is reduced to [0, 2 pi) first
+            const double d = (double)n - 0.5 * (double)p.N;
+            double s, c;
+            sincos(kTwoPi * t + z * d * d, &s, &c);
+            v = make_float2((float)c, (float)s);
+        }
+        p.out[(size_t)b * n_el + i] = v;
+    }
+}
+
+// U0 = exp(i phase), float64 sine and cosine of the float32 phase
+__global__ void __launch_bounds__(256) spot_phase_kernel(const float* phase, float2* u, long long n) {
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        double s, c;
+        sincos((double)phase[i], &s, &c);
+        u[i] = make_float2((float)c, (float)s);
+    }
+}
+
+// ---- fields: V partials ---------------------------------------------------
+struct FieldsParams {
+    const float2* u;    // [B][H][W]
+    const float* ain;   // [H][W] or nullptr
+    const float2* px;   // [B][W][Mp]
+    const float2* py;   // [B][H][Mp]
+    double2* partial;   // [B][units][Mp]
+    int H, W, Mp;
+    int col_splits, cols_per_split, units;
+};
+
+// Four waves per workgroup; each wave takes 32 rows x cols_per_split columns of
+// the field against 32 traps (one accumulator tile each for re and im) through
+// an LDS tile of its own, and the workgroup folds its four partial V in order:
+// one partial per 128 rows x cols_per_split columns. All four waves run the
+// same column range, so they pass the same barriers; a wave past the last row
+// works on zeros. grid = (groups of 4 row tiles x column splits, 32-trap tiles, batch).
+__global__ void __launch_bounds__(kFieldsThreads) spot_fields_kernel(FieldsParams p) {
+    __shared__ float tiles[kWaves][kTile * kLdsStride];
+    __shared__ double2 vsum[kWaves][kTile];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
+    float* tile = tiles[wave];
+    const int unit = blockIdx.x, rg = unit / p.col_splits, cs = unit - rg * p.col_splits;
+    const int b = blockIdx.z, m0 = blockIdx.y * kTile;
+    const int row0 = (rg * kWaves + wave) * kTile;
+    const int c_begin = cs * p.cols_per_split, c_end = min(p.W, c_begin + p.cols_per_split);
+    const float2* u = p.u + (size_t)b * p.H * p.W;
+    const float2* px = p.px + (size_t)b * p.W * p.Mp + m0 + li;
+    const float2* py = p.py + (size_t)b * p.H * p.Mp + m0 + li;
+
+    f32x16 are, aim;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) are[r] = aim[r] = 0.0f;
+
+    // Registers carry the next tile of the field (ut, at) and the table rows of
+    // the next eight steps (q0 / q1) while the matrix cores work on this one.
+    constexpr int kHalf = kTile / 4;  // steps per half tile (a step = 2 columns)
+    float2 ut[16], q0[kHalf], q1[kHalf];
+    float at[16];
+    // a 32 x 32 tile of the field: lanes 0-31 one row, lanes 32-63 the next (256 B each)
+    auto load_tile = [&](int c0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int gr = row0 + 2 * r + lh, gc = c0 + li;
+            ut[r] = make_float2(0.0f, 0.0f);
+            at[r] = 1.0f;
+            if (gr < p.H && gc < c_end) {
+                ut[r] = u[(size_t)gr * p.W + gc];
+                if (p.ain) at[r] = p.ain[(size_t)gr * p.W + gc];
+            }
+        }
+    };
+    // lane (m, h): Px of column c0 + 2 (j0 + s) + h; columns past the edge read the last one (their field is zero)
+    auto load_q = [&](float2(&q)[kHalf], int c0, int j0) {
+#pragma unroll
+        for (int s = 0; s < kHalf; ++s) q[s] = px[(size_t)min(c0 + 2 * (j0 + s) + lh, p.W - 1) * p.Mp];
+    };
+    auto mma = [&](const float2(&q)[kHalf], int j0) {
+#pragma unroll
+        for (int s = 0; s < kHalf; ++s) {
+            // lane (i, h): pixel (row0 + i, c0 + 2 (j0 + s) + h)
+            const float2 a = *reinterpret_cast<const float2*>(&tile[li * kLdsStride + 4 * (j0 + s) + 2 * lh]);
+            are = mfma(a.x, q[s].x, are);
+            aim = mfma(a.x, -q[s].y, aim);
+            are = mfma(a.y, q[s].y, are);
+            aim = mfma(a.y, q[s].x, aim);
+        }
+    };
+
+    load_tile(c_begin);
+    load_q(q0, c_begin, 0);
+    for (int c0 = c_begin; c0 < c_end; c0 += kTile) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            *reinterpret_cast<float2*>(&tile[(2 * r + lh) * kLdsStride + 2 * li]) =
+                make_float2(ut[r].x * at[r], ut[r].y * at[r]);
+        __syncthreads();
+        load_q(q1, c0, kHalf);
+        load_tile(c0 + kTile);  // past c_end: zeros, nothing is read
+        mma(q0, 0);
+        load_q(q0, c0 + kTile, 0);
+        mma(q1, kHalf);
+        __syncthreads();
+    }
+
+    // V partial = sum over the tile's rows of conj(Py) R, in float64; lane (m, h) holds 16 rows of trap m
+    double vr = 0.0, vi = 0.0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int gr = row0 + acc_row(r, lh);
+        if (gr < p.H) {
+            const float2 y = py[(size_t)gr * p.Mp];
+            const double rr = are[r], ri = aim[r];
+            vr += (double)y.x * rr + (double)y.y * ri;
+            vi += (double)y.x * ri - (double)y.y * rr;
+        }
+    }
+    vr += __shfl_xor(vr, 32);
+    vi += __shfl_xor(vi, 32);
+    if (lh == 0) vsum[wave][li] = make_double2(vr, vi);
+    __syncthreads();
+    if (threadIdx.x < kTile) {
+        double2 v = vsum[0][li];
+#pragma unroll
+        for (int k = 1; k < kWaves; ++k) {
+            v.x += vsum[k][li].x;
+            v.y += vsum[k][li].y;
+        }
+        p.partial[((size_t)b * p.units + unit) * p.Mp + m0 + li] = v;
+    }
+}
+
+// ---- update: fold, statistics, weights, coefficients ----------------------
+struct UpdateParams {
+    const double2* partial;  // [B][units][Mp]
+    const double* a_t;       // [B][Mp] sqrt(I)
+    const double* w_in;      // [B][Mp]
+    double* w_out;           // [B][Mp]
+    double2* v;              // [B][Mp]
+    float2* c;               // [B][Mp]
+    double* stats;           // [B][max_loops][4], this iteration's row at + 4 it
+    int M, Mp, units, max_loops, it;
+    double feedback, inv_norm;  // inv_norm = 1 / (H W sum a^2)
+};
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// the same value in every thread, in an order fixed by the thread index alone
+__device__ __forceinline__ double block_sum(double v, double* sh) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < kUpdThreads / 64; ++i) s += sh[i];
+    return s;
+}
+
+__device__ __forceinline__ double block_min(double v, double* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = sh[0];
+#pragma unroll
+    for (int i = 1; i < kUpdThreads / 64; ++i) s = fmin(s, sh[i]);
+    return s;
+}
+
+__global__ void __launch_bounds__(kUpdThreads) spot_update_kernel(UpdateParams p) {
+    __shared__ double2 fold[kUpdThreads];
+    __shared__ double red[kUpdThreads / 64];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const bool live = t < p.M;
+
+    // fold the partials: group g takes units g, g + G, ...; the groups are then added in order
+    const int groups = kUpdThreads / p.Mp;
+    const int g = t / p.Mp, mm = t - g * p.Mp;
+    double2 acc = make_double2(0.0, 0.0);
+    if (g < groups) {
+        const double2* src = p.partial + (size_t)b * p.units * p.Mp + mm;
+        // eight loads in flight, added in the order of the units
+        for (int u = g; u < p.units; u += 8 * groups) {
+            double2 d[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int uu = u + i * groups;
+                d[i] = uu < p.units ? src[(size_t)uu * p.Mp] : make_double2(0.0, 0.0);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                acc.x += d[i].x;
+                acc.y += d[i].y;
+            }
+        }
+    }
+    fold[t] = acc;
+    __syncthreads();
+    double vr = 0.0, vi = 0.0;
+    if (live) {
+        for (int k = 0; k < groups; ++k) {
+            vr += fold[k * p.Mp + t].x;
+            vi += fold[k * p.Mp + t].y;
+        }
+    }
+    const size_t at = (size_t)b * p.Mp + t;
+    const double a_t = live ? p.a_t[at] : 1.0;
+    const double e = vr * vr + vi * vi, amp = sqrt(e);
+    const double q = live ? e / (a_t * a_t) : 0.0;
+
+    // statistics of this iteration's field (before the update)
+    const double sum_e = block_sum(live ? e : 0.0, red);
+    const double mean_q = block_sum(q, red) / p.M;
+    const double r = q / mean_q;
+    const double mean_r = block_sum(live ? r : 0.0, red) / p.M;
+    const double dev = live ? (r - mean_r) * (r - mean_r) : 0.0;
+    const double var_r = block_sum(dev, red) / p.M;
+    const double min_r = block_min(live ? r : INFINITY, red);
+    const double max_r = -block_min(live ? -r : INFINITY, red);
+    if (t == 0) {
+        double* st = p.stats + ((size_t)b * p.max_loops + p.it) * 4;
+        st[0] = sum_e * p.inv_norm;
+        st[1] = sqrt(var_r);
+        st[2] = min_r;
+        st[3] = max_r;
+    }
+
+    // weights: w *= (a_T / |V|)^p where |V| > 0, factor clamped to [2^-64, 2^64]; then mean 1
+    double w = live ? p.w_in[at] : 0.0;
+    if (live && amp > 0.0) {
+        double f = pow(a_t / amp, p.feedback);
+        f = fmin(fmax(f, 0x1p-64), 0x1p64);
+        w *= f;
+    }
+    const double mean_w = block_sum(w, red) / p.M;
+    w /= mean_w;
+    if (t < p.Mp) {
+        float2 c = make_float2(0.0f, 0.0f);
+        if (live) {
+            const double s = a_t * w;
+            c = amp > 0.0 ? make_float2((float)(s * (vr / amp)), (float)(s * (vi / amp))) : make_float2((float)s, 0.0f);
+            p.w_out[at] = w;
+        }
+        p.v[at] = make_double2(vr, vi);
+        p.c[at] = c;
+    }
+}
+
+// ---- superposition: U = S / |S| -------------------------------------------
+struct SuperposeParams {
+    const float2* pyt;  // [B][Mp][H]
+    const float2* pxt;  // [B][Mp][W]
+    const float2* c;    // [B][Mp]
+    float2* u;          // [B][H][W]
+    float* phase;       // [B][H][W] or nullptr (only the run's last iteration stores it)
+    int H, W, M, Mp;
+};
+
+// One wave per 32 x 32 output tile, four adjacent column tiles per workgroup (a
+// workgroup puts one wave on each SIMD of its CU). grid = (column tiles / 4, row tiles, batch).
+__global__ void __launch_bounds__(kFieldsThreads) spot_superpose_kernel(SuperposeParams p) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
+    const int b = blockIdx.z, row0 = blockIdx.y * kTile, col0 = (blockIdx.x * kWaves + wave) * kTile;
+    if (col0 >= p.W) return;  // no barriers below
+    // rows / columns past the edge read the last valid line; their results are not stored
+    const float2* py = p.pyt + (size_t)b * p.Mp * p.H + min(row0 + li, p.H - 1);
+    const float2* px = p.pxt + (size_t)b * p.Mp * p.W + min(col0 + li, p.W - 1);
+    const float2* c = p.c + (size_t)b * p.Mp;
+    f32x16 sre, sim;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sre[r] = sim[r] = 0.0f;
+    // Groups of 8 steps = 16 traps (the padded columns are zero and 16 divides into Mp); the next
+    // group's table rows and coefficients are in flight while the matrix cores work on this one.
+    constexpr int kGroup = 8;
+    float2 y[kGroup], x[kGroup], cm[kGroup], yn[kGroup], xn[kGroup], cn[kGroup];
+    const int groups = (p.M + 2 * kGroup - 1) / (2 * kGroup);
+#pragma unroll
+    for (int s = 0; s < kGroup; ++s) {
+        const int m = 2 * s + lh;
+        y[s] = py[(size_t)m * p.H];
+        x[s] = px[(size_t)m * p.W];
+        cm[s] = c[m];
+    }
+    for (int g = 0; g < groups; ++g) {
+        if (g + 1 < groups) {
+#pragma unroll
+            for (int s = 0; s < kGroup; ++s) {
+                const int m = 2 * (kGroup * (g + 1) + s) + lh;
+                yn[s] = py[(size_t)m * p.H];
+                xn[s] = px[(size_t)m * p.W];
+                cn[s] = c[m];
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < kGroup; ++s) {
+            const float ar = y[s].x * cm[s].x - y[s].y * cm[s].y, ai = y[s].x * cm[s].y + y[s].y * cm[s].x;
+            sre = mfma(ar, x[s].x, sre);
+            sim = mfma(ar, x[s].y, sim);
+            sre = mfma(ai, -x[s].y, sre);
+            sim = mfma(ai, x[s].x, sim);
+        }
+        if (g + 1 == groups) break;
+#pragma unroll
+        for (int s = 0; s < kGroup; ++s) {
+            y[s] = yn[s];
+            x[s] = xn[s];
+            cm[s] = cn[s];
+        }
+    }
+    const int gc = col0 + li;
+    if (gc >= p.W) return;
+    const size_t base = (size_t)b * p.H * p.W + gc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int gr = row0 + acc_row(r, lh);
+        if (gr >= p.H) continue;
+        float sr = sre[r], si = sim[r];
+        float2 v = make_float2(1.0f, 0.0f);  // S = 0: angle 0
+        const float big = fmaxf(fabsf(sr), fabsf(si));
+        if (big > 0.0f) {
+            int ex;  // scale by a power of two: no overflow or underflow of the square
+            (void)frexpf(big, &ex);
+            sr = ldexpf(sr, -ex);
+            si = ldexpf(si, -ex);
+            const float inv = rsqrtf(sr * sr + si * si);
+            v = make_float2(sr * inv, si * inv);
+        }
+        p.u[base + (size_t)gr * p.W] = v;
+        if (p.phase) p.phase[base + (size_t)gr * p.W] = (float)atan2((double)sim[r], (double)sre[r]);
+    }
+}
+
+int grid_for(long long n) { return (int)std::min<long long>(8192, (n + 255) / 256); }
+int padded_traps(int m) { return (m + kTile - 1) / kTile * kTile; }
+
+template <typename T>
+void dev_free(T*& p) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+}
+
+}  // namespace
+
+using slm::fail;
+
+struct slm_spots {
+    int B = 0, H = 0, W = 0, max_traps = 0, has_ain = 0, max_loops = 0;
+    int M = 0, Mp = 0;  // the current list (0 = none set)
+    int col_splits = 1, cols_per_split = 0, units = 0;
+    double feedback = 1.0, sum_a2 = 0.0;
+    bool ain_set = false, custom_phase = false, u0_valid = false, has_run = false;
+    int last_loops = 0;
+    hipStream_t stream = nullptr;
+    float* ain = nullptr;
+    float2 *u0 = nullptr, *u = nullptr;  // the start (runs read it, never write it) and the state
+    float* phase = nullptr;
+    float2 *py = nullptr, *px = nullptr, *pyt = nullptr, *pxt = nullptr;
+    double *coords = nullptr;  // ys, xs, zs [3][B][max_traps]
+    double *a_t = nullptr, *w0 = nullptr, *w = nullptr, *stats = nullptr;
+    double2 *v = nullptr, *partial = nullptr;
+    size_t partial_cap = 0;
+    float2 *c = nullptr, *c0 = nullptr;
+    std::vector<double> host_a_t;  // [B][M], for the default start
+};
+
+namespace {
+
+void spots_free(slm_spots* s) {
+    if (!s) return;
+    dev_free(s->ain);
+    dev_free(s->u0);
+    dev_free(s->u);
+    dev_free(s->phase);
+    dev_free(s->py);
+    dev_free(s->px);
+    dev_free(s->pyt);
+    dev_free(s->pxt);
+    dev_free(s->coords);
+    dev_free(s->a_t);
+    dev_free(s->w0);
+    dev_free(s->w);
+    dev_free(s->stats);
+    dev_free(s->v);
+    dev_free(s->partial);
+    dev_free(s->c);
+    dev_free(s->c0);
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    delete s;
+}
+
+int up(slm_spots* s, void* dst, const void* src, size_t bytes) {
+    return slm::copy_sync(dst, src, bytes, hipMemcpyHostToDevice, s->stream);
+}
+int down(slm_spots* s, void* dst, const void* src, size_t bytes) {
+    return slm::copy_sync(dst, src, bytes, hipMemcpyDeviceToHost, s->stream);
+}
+
+SuperposeParams superpose_params(slm_spots* s, const float2* c, float2* u, float* phase) {
+    SuperposeParams p{};
+    p.pyt = s->pyt;
+    p.pxt = s->pxt;
+    p.c = c;
+    p.u = u;
+    p.phase = phase;
+    p.H = s->H;
+    p.W = s->W;
+    p.M = s->M;
+    p.Mp = s->Mp;
+    return p;
+}
+
+int launch_superpose(slm_spots* s, const float2* c, float2* u, float* phase) {
+    const dim3 grid((s->W + kWaves * kTile - 1) / (kWaves * kTile), (s->H + kTile - 1) / kTile, s->B);
+    hipLaunchKernelGGL(spot_superpose_kernel, grid, dim3(kFieldsThreads), 0, s->stream, superpose_params(s, c, u, phase));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_fields(slm_spots* s, const float2* u) {
+    FieldsParams p{};
+    p.u = u;
+    p.ain = s->ain_set ? s->ain : nullptr;
+    p.px = s->px;
+    p.py = s->py;
+    p.partial = s->partial;
+    p.H = s->H;
+    p.W = s->W;
+    p.Mp = s->Mp;
+    p.col_splits = s->col_splits;
+    p.cols_per_split = s->cols_per_split;
+    p.units = s->units;
+    hipLaunchKernelGGL(spot_fields_kernel, dim3(s->units, s->Mp / kTile, s->B), dim3(kFieldsThreads), 0, s->stream,
+                       p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int launch_update(slm_spots* s, int it) {
+    UpdateParams p{};
+    p.partial = s->partial;
+    p.a_t = s->a_t;
+    p.w_in = it == 0 ? s->w0 : s->w;
+    p.w_out = s->w;
+    p.v = s->v;
+    p.c = s->c;
+    p.stats = s->stats;
+    p.M = s->M;
+    p.Mp = s->Mp;
+    p.units = s->units;
+    p.max_loops = s->max_loops;
+    p.it = it;
+    p.feedback = s->feedback;
+    p.inv_norm = 1.0 / ((double)s->H * s->W * s->sum_a2);
+    hipLaunchKernelGGL(spot_update_kernel, dim3(s->B), dim3(kUpdThreads), 0, s->stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// the start of a run without a caller's phase: angle(sum_m a_T,m exp(i (D_m + theta_m)))
+int default_start(slm_spots* s) {
+    if (s->custom_phase || s->u0_valid) return 0;
+    std::vector<float2> c0((size_t)s->B * s->Mp, make_float2(0.0f, 0.0f));
+    for (int b = 0; b < s->B; ++b)
+        for (int m = 0; m < s->M; ++m) {
+            double th = (double)m * kGolden;
+            th = kTwoPi * (th - std::floor(th));
+            const double a = s->host_a_t[(size_t)b * s->M + m];
+            c0[(size_t)b * s->Mp + m] = make_float2((float)(a * std::cos(th)), (float)(a * std::sin(th)));
+        }
+    RC(up(s, s->c0, c0.data(), c0.size() * sizeof(float2)));
+    RC(launch_superpose(s, s->c0, s->u0, nullptr));
+    s->u0_valid = true;
+    return 0;
+}
+
+struct Timer {
+    std::vector<hipEvent_t> ev;
+    std::vector<int> cls;
+    hipStream_t st;
+    bool on;
+    int begin(int c) {
+        if (!on) return 0;
+        hipEvent_t a = nullptr, b = nullptr;
+        HIP_TRY(hipEventCreate(&a));
+        ev.push_back(a);
+        HIP_TRY(hipEventCreate(&b));
+        ev.push_back(b);
+        cls.push_back(c);
+        HIP_TRY(hipEventRecord(a, st));
+        return 0;
+    }
+    int end() {
+        if (!on) return 0;
+        HIP_TRY(hipEventRecord(ev.back(), st));
+        return 0;
+    }
+    ~Timer() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+};
+
+int run_loops(slm_spots* s, int loops, double* us_per_class) {
+    if (!s) return fail(SLM_ERR_ARG, "null spots handle");
+    if (!s->M) return fail(SLM_ERR_STATE, "slm_spots_run before slm_spots_set_traps");
+    if (s->has_ain && !s->ain_set) return fail(SLM_ERR_STATE, "slm_spots_run before slm_spots_set_ain");
+    if (loops < 1 || loops > s->max_loops)
+        return fail(SLM_ERR_ARG, "loops %d outside 1 .. max_loops %d", loops, s->max_loops);
+    RC(slm::ensure_device());
+    RC(default_start(s));
+    Timer tm{{}, {}, s->stream, us_per_class != nullptr};
+    for (int it = 0; it < loops; ++it) {
+        RC(tm.begin(SLM_SPOTS_KERNEL_FIELDS));
+        RC(launch_fields(s, it == 0 ? s->u0 : s->u));
+        RC(tm.end());
+        RC(tm.begin(SLM_SPOTS_KERNEL_UPDATE));
+        RC(launch_update(s, it));
+        RC(tm.end());
+        RC(tm.begin(SLM_SPOTS_KERNEL_SUPERPOSE));
+        RC(launch_superpose(s, s->c, s->u, it == loops - 1 ? s->phase : nullptr));
+        RC(tm.end());
+    }
+    s->has_run = true;
+    s->last_loops = loops;
+    if (us_per_class) {
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        for (int k = 0; k < SLM_SPOTS_NUM_KERNEL_CLASSES; ++k) us_per_class[k] = 0.0;
+        for (size_t k = 0; k < tm.cls.size(); ++k) {
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]));
+            us_per_class[tm.cls[k]] += 1e3 * ms;
+        }
+    }
+    return 0;
+}
+
+// how the fields product is cut for Mp: a function of the shape and the list alone, never of the batch
+void plan_fields(slm_spots* s) {
+    const int row_tiles = (s->H + kTile - 1) / kTile, chunks = (s->W + kTile - 1) / kTile;
+    const int groups = s->Mp / kTile;
+    int splits = (kTargetWaves + row_tiles * groups - 1) / (row_tiles * groups);
+    splits = std::max(1, std::min(splits, chunks));
+    const int chunks_per = (chunks + splits - 1) / splits;
+    s->col_splits = (chunks + chunks_per - 1) / chunks_per;
+    s->cols_per_split = chunks_per * kTile;
+    s->units = (row_tiles + kWaves - 1) / kWaves * s->col_splits;
+}
+
+int launch_table(slm_spots* s, const double* pos, const double* z, float2* out, int n, int transposed) {
+    TableParams p{pos, z, out, n, s->M, s->Mp, transposed};
+    hipLaunchKernelGGL(spot_table_kernel, dim3(grid_for((long long)n * s->Mp), s->B), dim3(256), 0, s->stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int slm_spots_create(int batch, int height, int width, int max_traps, int has_ain, int max_loops, slm_spots** out) {
+    if (!out) return fail(SLM_ERR_ARG, "null output handle");
+    *out = nullptr;
+    if (batch < 1 || max_loops < 1) return fail(SLM_ERR_ARG, "batch and max_loops must be positive");
+    if (height < kMinSide || width < kMinSide || height > kMaxSide || width > kMaxSide)
+        return fail(SLM_ERR_ARG, "trap lists run on sides %d .. %d, got %d x %d", kMinSide, kMaxSide, height, width);
+    if (max_traps < 1 || max_traps > kMaxTraps)
+        return fail(SLM_ERR_ARG, "max_traps %d outside 1 .. %d", max_traps, kMaxTraps);
+    RC(slm::ensure_device());
+    slm_spots* s = new slm_spots;
+    s->B = batch;
+    s->H = height;
+    s->W = width;
+    s->max_traps = max_traps;
+    s->has_ain = has_ain != 0;
+    s->max_loops = max_loops;
+    s->sum_a2 = (double)height * width;
+    const size_t holo = (size_t)height * width, mp = padded_traps(max_traps), bm = (size_t)batch * mp;
+    int rc = 0;
+    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess)
+        rc = fail(SLM_ERR_HIP, "hipStreamCreate failed");
+    if (!rc && s->has_ain) rc = slm::dev_alloc(&s->ain, holo * sizeof(float));
+    if (!rc) rc = slm::dev_alloc(&s->u0, batch * holo * sizeof(float2));
+    if (!rc) rc = slm::dev_alloc(&s->u, batch * holo * sizeof(float2));
+    if (!rc) rc = slm::dev_alloc(&s->phase, batch * holo * sizeof(float));
+    if (!rc) rc = slm::dev_alloc(&s->py, bm * height * sizeof(float2));
+    if (!rc) rc = slm::dev_alloc(&s->pyt, bm * height * sizeof(float2));
+    if (!rc) rc = slm::dev_alloc(&s->px, bm * width * sizeof(float2));
+    if (!rc) rc = slm::dev_alloc(&s->pxt, bm * width * sizeof(float2));
+    if (!rc) rc = slm::dev_alloc(&s->coords, 3 * (size_t)batch * max_traps * sizeof(double));
+    if (!rc) rc = slm::dev_alloc(&s->a_t, bm * sizeof(double));
+    if (!rc) rc = slm::dev_alloc(&s->w0, bm * sizeof(double));
+    if (!rc) rc = slm::dev_alloc(&s->w, bm * sizeof(double));
+    if (!rc) rc = slm::dev_alloc(&s->v, bm * sizeof(double2));
+    if (!rc) rc = slm::dev_alloc(&s->c, bm * sizeof(float2));
+    if (!rc) rc = slm::dev_alloc(&s->c0, bm * sizeof(float2));
+    if (!rc) rc = slm::dev_alloc(&s->stats, (size_t)batch * max_loops * 4 * sizeof(double));
+    if (rc) {
+        spots_free(s);
+        return rc;
+    }
+    *out = s;
+    return 0;
+}
+
+int slm_spots_destroy(slm_spots* sp) {
+    if (sp) {
+        if (sp->stream) (void)hipStreamSynchronize(sp->stream);
+        spots_free(sp);
+    }
+    return 0;
+}
+
+int slm_spots_set_traps(slm_spots* s, int n_traps, const double* ys, const double* xs, const double* zs,
+                        const float* intensity) {
+    if (!s || !ys || !xs) return fail(SLM_ERR_ARG, "null argument");
+    if (n_traps < 1 || n_traps > s->max_traps)
+        return fail(SLM_ERR_ARG, "%d traps outside 1 .. max_traps %d", n_traps, s->max_traps);
+    const size_t n = (size_t)s->B * n_traps;
+    for (size_t i = 0; i < n; ++i) {
+        if (!std::isfinite(ys[i]) || !std::isfinite(xs[i]) || (zs && !std::isfinite(zs[i])))
+            return fail(SLM_ERR_ARG, "trap %zu has a non-finite coordinate", i);
+        if (intensity && !(intensity[i] > 0.0f && std::isfinite(intensity[i])))
+            return fail(SLM_ERR_ARG, "trap %zu: the intensity must be positive and finite", i);
+    }
+    RC(slm::ensure_device());
+    s->M = n_traps;
+    s->Mp = padded_traps(n_traps);
+    s->has_run = false;
+    s->u0_valid = false;
+    plan_fields(s);
+    const size_t need = (size_t)s->B * s->units * s->Mp * sizeof(double2);
+    if (need > s->partial_cap) {
+        dev_free(s->partial);
+        s->partial_cap = 0;
+        RC(slm::dev_alloc(&s->partial, need));
+        s->partial_cap = need;
+    }
+    std::vector<double> z0(n, 0.0);
+    double *dy = s->coords, *dx = dy + n, *dz = dx + n;
+    RC(up(s, dy, ys, n * sizeof(double)));
+    RC(up(s, dx, xs, n * sizeof(double)));
+    RC(up(s, dz, zs ? zs : z0.data(), n * sizeof(double)));
+    s->host_a_t.assign(n, 1.0);
+    std::vector<double> a_t((size_t)s->B * s->Mp, 1.0), ones((size_t)s->B * s->Mp, 1.0);
+    for (int b = 0; b < s->B; ++b)
+        for (int m = 0; m < n_traps; ++m) {
+            const double a = intensity ? std::sqrt((double)intensity[(size_t)b * n_traps + m]) : 1.0;
+            s->host_a_t[(size_t)b * n_traps + m] = a;
+            a_t[(size_t)b * s->Mp + m] = a;
+        }
+    RC(up(s, s->a_t, a_t.data(), a_t.size() * sizeof(double)));
+    RC(up(s, s->w0, ones.data(), ones.size() * sizeof(double)));
+    RC(launch_table(s, dy, dz, s->py, s->H, 0));
+    RC(launch_table(s, dy, dz, s->pyt, s->H, 1));
+    RC(launch_table(s, dx, dz, s->px, s->W, 0));
+    RC(launch_table(s, dx, dz, s->pxt, s->W, 1));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+
+int slm_spots_set_ain(slm_spots* s, const float* ain) {
+    if (!s || !ain) return fail(SLM_ERR_ARG, "null argument");
+    if (!s->has_ain) return fail(SLM_ERR_STATE, "the handle was created without a_in");
+    const size_t holo = (size_t)s->H * s->W;
+    double sum = 0.0;
+    for (size_t i = 0; i < holo; ++i) {
+        if (!std::isfinite(ain[i])) return fail(SLM_ERR_ARG, "a_in has a non-finite entry");
+        sum += (double)ain[i] * (double)ain[i];
+    }
+    if (!(sum > 0.0)) return fail(SLM_ERR_ARG, "a_in is zero everywhere");
+    RC(slm::ensure_device());
+    RC(up(s, s->ain, ain, holo * sizeof(float)));
+    s->sum_a2 = sum;
+    s->ain_set = true;
+    return 0;
+}
+
+int slm_spots_set_phase(slm_spots* s, const float* phase) {
+    if (!s) return fail(SLM_ERR_ARG, "null spots handle");
+    RC(slm::ensure_device());
+    s->u0_valid = false;
+    s->custom_phase = phase != nullptr;
+    if (!phase) return 0;
+    const long long n = (long long)s->B * s->H * s->W;
+    // the float32 phase passes through the state buffer on its way to the start field
+    RC(up(s, s->phase, phase, n * sizeof(float)));
+    hipLaunchKernelGGL(spot_phase_kernel, dim3(grid_for(n)), dim3(256), 0, s->stream, s->phase, s->u0, n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->has_run = false;
+    return 0;
+}
+
+int slm_spots_set_weights(slm_spots* s, const float* weights) {
+    if (!s) return fail(SLM_ERR_ARG, "null spots handle");
+    if (!s->M) return fail(SLM_ERR_STATE, "slm_spots_set_weights before slm_spots_set_traps");
+    std::vector<double> w((size_t)s->B * s->Mp, 1.0);
+    if (weights)
+        for (int b = 0; b < s->B; ++b)
+            for (int m = 0; m < s->M; ++m) {
+                const float v = weights[(size_t)b * s->M + m];
+                if (!(v > 0.0f && std::isfinite(v)))
+                    return fail(SLM_ERR_ARG, "weight %d of hologram %d is not positive and finite", m, b);
+                w[(size_t)b * s->Mp + m] = v;
+            }
+    RC(slm::ensure_device());
+    return up(s, s->w0, w.data(), w.size() * sizeof(double));
+}
+
+int slm_spots_set_feedback(slm_spots* s, float feedback) {
+    if (!s) return fail(SLM_ERR_ARG, "null spots handle");
+    if (!(feedback >= 0.0f) || !std::isfinite(feedback))
+        return fail(SLM_ERR_ARG, "feedback must be finite and >= 0, got %g", (double)feedback);
+    s->feedback = feedback;
+    return 0;
+}
+
+int slm_spots_run(slm_spots* s, int loops) { return run_loops(s, loops, nullptr); }
+
+int slm_spots_run_timed(slm_spots* s, int loops, double* us_per_class) {
+    if (!us_per_class) return fail(SLM_ERR_ARG, "null argument");
+    return run_loops(s, loops, us_per_class);
+}
+
+int slm_spots_read(slm_spots* s, float* phase, double* fields, double* stats, float* weights) {
+    if (!s) return fail(SLM_ERR_ARG, "null spots handle");
+    if (!s->has_run) return fail(SLM_ERR_STATE, "slm_spots_read before a run");
+    RC(slm::ensure_device());
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (phase) RC(down(s, phase, s->phase, (size_t)s->B * s->H * s->W * sizeof(float)));
+    const size_t bm = (size_t)s->B * s->Mp;
+    if (fields) {
+        std::vector<double2> v(bm);
+        RC(down(s, v.data(), s->v, bm * sizeof(double2)));
+        for (int b = 0; b < s->B; ++b)
+            for (int m = 0; m < s->M; ++m) {
+                fields[2 * ((size_t)b * s->M + m)] = v[(size_t)b * s->Mp + m].x;
+                fields[2 * ((size_t)b * s->M + m) + 1] = v[(size_t)b * s->Mp + m].y;
+            }
+    }
+    if (stats) {
+        std::vector<double> st((size_t)s->B * s->max_loops * 4);
+        RC(down(s, st.data(), s->stats, st.size() * sizeof(double)));
+        for (int b = 0; b < s->B; ++b)
+            std::copy_n(&st[(size_t)b * s->max_loops * 4], (size_t)s->last_loops * 4,
+                        &stats[(size_t)b * s->last_loops * 4]);
+    }
+    if (weights) {
+        std::vector<double> w(bm);
+        RC(down(s, w.data(), s->w, bm * sizeof(double)));
+        for (int b = 0; b < s->B; ++b)
+            for (int m = 0; m < s->M; ++m) weights[(size_t)b * s->M + m] = (float)w[(size_t)b * s->Mp + m];
+    }
+    return 0;
+}
+
+int slm_spots_info(slm_spots* s, int* info) {
+    if (!s || !info) return fail(SLM_ERR_ARG, "null argument");
+    if (!s->M) return fail(SLM_ERR_STATE, "slm_spots_info before slm_spots_set_traps");
+    info[0] = s->Mp;
+    info[1] = s->units;
+    info[2] = s->cols_per_split;
+    info[3] = kWaves;
+    return 0;
+}
+
+int slm_spots_fields(int batch, int height, int width, int n_traps, const double* ys, const double* xs,
+                     const double* zs, const float* ain, const float* phase, double* fields_out) {
+    if (!phase || !fields_out) return fail(SLM_ERR_ARG, "null argument");
+    slm_spots* s = nullptr;
+    RC(slm_spots_create(batch, height, width, n_traps, ain != nullptr, 1, &s));
+    int rc = slm_spots_set_traps(s, n_traps, ys, xs, zs, nullptr);
+    if (!rc && ain) rc = slm_spots_set_ain(s, ain);
+    if (!rc) rc = slm_spots_set_phase(s, phase);
+    if (!rc) rc = launch_fields(s, s->u0);
+    if (!rc) rc = launch_update(s, 0);
+    if (!rc) {
+        s->has_run = true;
+        s->last_loops = 1;
+        rc = slm_spots_read(s, nullptr, fields_out, nullptr, nullptr);
+    }
+    slm_spots_destroy(s);
+    return rc;
+}
+
+int slm_spots_superpose(int batch, int height, int width, int n_traps, const double* ys, const double* xs,
+                        const double* zs, const double* c_re_im, float* phase_out) {
+    if (!c_re_im || !phase_out) return fail(SLM_ERR_ARG, "null argument");
+    slm_spots* s = nullptr;
+    RC(slm_spots_create(batch, height, width, n_traps, 0, 1, &s));
+    int rc = slm_spots_set_traps(s, n_traps, ys, xs, zs, nullptr);
+    if (!rc) {
+        std::vector<float2> c((size_t)batch * s->Mp, make_float2(0.0f, 0.0f));
+        for (int b = 0; b < batch; ++b)
+            for (int m = 0; m < n_traps; ++m)
+                c[(size_t)b * s->Mp + m] = make_float2((float)c_re_im[2 * ((size_t)b * n_traps + m)],
+                                                       (float)c_re_im[2 * ((size_t)b * n_traps + m) + 1]);
+        rc = up(s, s->c, c.data(), c.size() * sizeof(float2));
+    }
+    if (!rc) rc = launch_superpose(s, s->c, s->u, s->phase);
+    if (!rc) {
+        s->has_run = true;
+        s->last_loops = 1;
+        rc = slm_spots_read(s, phase_out, nullptr, nullptr, nullptr);
+    }
+    slm_spots_destroy(s);
+    return rc;
+}
+
+}  // extern "C"

@@ -12,12 +12,19 @@ DESIGN.md section 7).
   SLM window.
 * ``trap_frame(shape, coords, which, mask, mask_flag, ct2pi)`` — both fused in
   one launch: what a key press of the trap-moving loop costs.
+* ``trap_array_hologram`` / ``trap_array_frame`` — no reference counterpart:
+  the hologram of a whole list of traps (fractional positions, a defocus per
+  trap, uniform or chosen intensities) by spot-based weighted GS on the GPU
+  (slm_spots_*), on any panel shape.
 """
 from __future__ import annotations
+
+import collections
 
 import numpy as np
 
 from . import _lib
+from . import constants
 
 
 def _trap_index(black_image: np.ndarray, coords, which):
@@ -56,6 +63,92 @@ def hologram_frame(hologram: np.ndarray, mask, mask_flag: bool, ct2pi) -> np.nda
     ((hologram [+ mask]) % 2pi * ct2pi / 2pi).astype(uint8)."""
     return _lib.quantize(np.asarray(hologram, dtype=np.float64), mask if mask_flag else None, ct2pi,
                          _lib.QUANT_ASTYPE)
+
+
+# ---------------------------------------------------------------------------
+# trap lists: the multi-trap counterpart of update_hologram (no reference
+# counterpart; slm_spots_* in include/slm_hip.h)
+# ---------------------------------------------------------------------------
+_SPOTS: "collections.OrderedDict[tuple, _lib.Spots]" = collections.OrderedDict()
+_MAX_SPOTS = 4
+
+
+def _get_spots(batch, h, w, n_traps, has_ain, loops) -> _lib.Spots:
+    """Spots handles are cached per (B, H, W, max_traps, has_ain), max_traps
+    being the trap count rounded up to a multiple of 32."""
+    max_traps = min(_lib.SPOTS_MAX_TRAPS, -(-n_traps // 32) * 32)
+    key = (batch, h, w, max(max_traps, n_traps), bool(has_ain))
+    sp = _SPOTS.pop(key, None)
+    if sp is not None and sp.max_loops < loops:
+        sp.close()
+        sp = None
+    if sp is None:
+        while len(_SPOTS) >= _MAX_SPOTS:
+            _SPOTS.popitem(last=False)[1].close()
+        sp = _lib.Spots(batch, h, w, key[3], has_ain, max(loops, 64))
+    _SPOTS[key] = sp
+    return sp
+
+
+def clear_spots() -> None:
+    while _SPOTS:
+        _SPOTS.popitem()[1].close()
+
+
+def lens_to_z(focal_length: float) -> float:
+    """The defocus z (radians per pixel^2) of a lens of this focal length in
+    metres: the paraxial form of generate_hologram.lens(),
+    -pi px_distance^2 / (wavelength f)."""
+    return -np.pi * constants.px_distance ** 2 / (constants.wavelength * float(focal_length))
+
+
+def trap_array_hologram(shape, ys, xs, zs=None, intensity=None, loops=30, feedback=1.0, ain=None,
+                        initial_phase=None, initial_weights=None):
+    """Weighted GS on a list of traps (spot form, slm_spots_*): positions ys, xs
+    in far-field pixels (fractions and negative values allowed), defocus zs in
+    radians per pixel^2 (lens_to_z), target intensities. One list [M], or a
+    batch [B][M] of lists for B holograms. Returns (hologram float64 as
+    update_hologram's, per-trap intensities |V_m|^2 of the last iteration, the
+    statistics [loops][4] = (efficiency, uniformity, min, max of the
+    normalised intensities) and the weights); with a batch input every result
+    has the leading axis B."""
+    h, w = int(shape[0]), int(shape[1])
+    y = np.asarray(ys, dtype=np.float64)
+    single = y.ndim < 2
+    y = np.atleast_2d(y)
+    b, m = y.shape
+
+    def per_trap(v, name):
+        if v is None:
+            return None
+        v = np.atleast_2d(np.asarray(v, dtype=np.float64))
+        if v.shape != (b, m):
+            raise ValueError(f"{name} has shape {v.shape}, the trap lists {(b, m)}")
+        return v
+
+    sp = _get_spots(b, h, w, m, ain is not None, int(loops))
+    sp.set_traps(y, per_trap(xs, "xs"), per_trap(zs, "zs"), per_trap(intensity, "intensity"))
+    if ain is not None:
+        sp.set_ain(ain)
+    sp.set_feedback(feedback)
+    sp.set_phase(None if initial_phase is None else np.asarray(initial_phase).reshape(b, h, w))
+    sp.set_weights(None if initial_weights is None else per_trap(initial_weights, "initial_weights"))
+    sp.run(int(loops))
+    phase, v, stats, weights = sp.read()
+    holo, inten = phase.astype(np.float64), v.real ** 2 + v.imag ** 2
+    if single:
+        return holo[0], inten[0], stats[0], weights[0]
+    return holo, inten, stats, weights
+
+
+def trap_array_frame(shape, ys, xs, zs=None, intensity=None, loops=30, feedback=1.0, ain=None, initial_phase=None,
+                     initial_weights=None, mask=None, mask_flag: bool = True, ct2pi=256):
+    """trap_array_hologram plus hologram_frame's quantisation: returns
+    (hologram, frame uint8, intensities, statistics, weights)."""
+    holo, inten, stats, weights = trap_array_hologram(shape, ys, xs, zs, intensity, loops, feedback, ain,
+                                                      initial_phase, initial_weights)
+    frame = hologram_frame(holo, mask, mask_flag and mask is not None, ct2pi)
+    return holo, frame, inten, stats, weights
 
 
 def trap_frame(shape, coords, which, mask=None, mask_flag: bool = True, ct2pi=256):
