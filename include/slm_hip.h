@@ -361,7 +361,59 @@ int slm_quantize(const void* src, int src_type, const double* mask, int batch, i
  *   per workgroup of the two product kernels (info holds 4 ints).
  * slm_spots_fields / slm_spots_superpose: one-shot test entries for the two
  *   products alone: V [batch][n_traps][2] of exp(i phase) (times a_in), and
- *   angle(sum_m c_m exp(i D_m)) for complex c [batch][n_traps][2].           */
+ *   angle(sum_m c_m exp(i D_m)) for complex c [batch][n_traps][2].
+ *
+ * Trap trajectories: F frames of a moving list of the same M traps (trap m of
+ * frame f is trap m of frame f-1, moved) as one chain enqueued on the handle's
+ * stream, with everything above unchanged per iteration:
+ *     frame 0:   start phase = the handle's (slm_spots_set_phase) or the default
+ *                start for list 0; weights = weights0 or ones; at most
+ *                loops_first iterations on list 0
+ *     frame f>0: tables and a_T of list f; start = the unit field U and the
+ *                weights w that frame f-1 ended with (U as it is on the device,
+ *                complex64, no float32 phase in between); at most `loops` iterations
+ *     stop:      tol > 0: the first iteration of a frame whose uniformity std(r)
+ *                (of the field entering that iteration) is <= tol still completes
+ *                and is the frame's last; iters[f] = its index + 1. Holograms of a
+ *                batch stop on their own. tol = 0: every frame runs its full count.
+ *     outputs of frame f, from its last executed iteration: phase float32, V, w
+ *                (mean 1), statistics rows 0 .. iters[f]-1 (later rows are 0),
+ *                iters[f], and frame = the SLM_QUANT_* `rule` of slm_quantize
+ *                applied to ((double)phase, mask, ct2pi), written by the
+ *                superposition kernel itself.
+ * So F frames of one list at n iterations each with tol = 0 are one
+ * slm_spots_run of F n iterations, and a sequence cut in two with `resume` is
+ * the uncut one, both bit for bit.
+ * slm_spots_sequence: ys, xs, zs (NULL = 0), intensity (NULL = 1) are
+ *   [n_frames][batch][n_traps]; weights0 [batch][n_traps] (NULL = ones; must be
+ *   NULL with resume). mask [height][width] float64 or NULL, ct2pi and rule as
+ *   slm_quantize. want_frames / want_phases != 0 keep the uint8 frames / the
+ *   float32 phases of every frame on the device for slm_spots_sequence_read.
+ *   Everything is checked on the host before anything is enqueued. SLM_ERR_ARG:
+ *   a non-finite coordinate, an intensity or weight that is not positive and
+ *   finite, n_traps outside 1 .. max_traps, n_frames < 1, loops_first or loops
+ *   outside 1 .. max_loops, tol negative or not finite, an unknown rule, ct2pi
+ *   not positive and finite (both checked whether or not frames are wanted),
+ *   weights0 with resume. SLM_ERR_STATE: has_ain without slm_spots_set_ain;
+ *   resume != 0 without a previous sequence of the same n_traps on this handle
+ *   or after any slm_spots_set_* or slm_spots_run since. SLM_ERR_HIP when a
+ *   sequence buffer cannot be allocated (they are sized at the call, only grow,
+ *   and are freed with the handle). The call uploads the coordinates of all
+ *   frames once, enqueues the chain (per frame: one launch that builds the four
+ *   tables from the device-resident coordinates, then the iterations; no host
+ *   synchronisation between frames) and returns.
+ *   With resume, frame 0 of the call is treated as a frame f > 0: it starts from
+ *   the U and w the previous sequence ended with and runs `loops` iterations.
+ *   The feedback exponent and a_in are the handle's. After a sequence the
+ *   handle is as after slm_spots_set_traps with the last frame's list: weights
+ *   back to ones, a caller's start phase still in force, slm_spots_read refuses
+ *   until the next slm_spots_run.
+ * slm_spots_sequence_read: waits for the chain, then copies what is asked for
+ *   (any pointer NULL): frames [n_frames][batch][h][w] uint8, phases
+ *   [n_frames][batch][h][w] float32, fields [n_frames][batch][n_traps][2], stats
+ *   [n_frames][batch][max(loops_first, loops)][4], weights
+ *   [n_frames][batch][n_traps], iters [n_frames][batch]. SLM_ERR_STATE before a
+ *   sequence, and for frames or phases the sequence was not asked to keep.    */
 #define SLM_SPOTS_KERNEL_FIELDS 0    /* spot_fields_kernel: V partials */
 #define SLM_SPOTS_KERNEL_UPDATE 1    /* spot_update_kernel: fold, statistics, weights */
 #define SLM_SPOTS_KERNEL_SUPERPOSE 2 /* spot_superpose_kernel: the next unit field (and the phase) */
@@ -379,6 +431,11 @@ int slm_spots_run(slm_spots* sp, int loops);
 int slm_spots_run_timed(slm_spots* sp, int loops, double* us_per_class);
 int slm_spots_read(slm_spots* sp, float* phase, double* fields, double* stats, float* weights);
 int slm_spots_info(slm_spots* sp, int* info);
+int slm_spots_sequence(slm_spots* sp, int n_frames, int n_traps, const double* ys, const double* xs, const double* zs,
+                       const float* intensity, const float* weights0, int loops_first, int loops, double tol,
+                       int resume, const double* mask, double ct2pi, int rule, int want_frames, int want_phases);
+int slm_spots_sequence_read(slm_spots* sp, unsigned char* frames, float* phases, double* fields, double* stats,
+                            float* weights, int* iters);
 int slm_spots_fields(int batch, int height, int width, int n_traps, const double* ys, const double* xs,
                      const double* zs, const float* ain, const float* phase, double* fields_out);
 int slm_spots_superpose(int batch, int height, int width, int n_traps, const double* ys, const double* xs,

@@ -131,6 +131,9 @@ _SIGNATURES = [
     ("slm_spots_run_timed", _c_int, [_vp, _c_int, _vp]),
     ("slm_spots_read", _c_int, [_vp, _vp, _vp, _vp, _vp]),
     ("slm_spots_info", _c_int, [_vp, _vp]),
+    ("slm_spots_sequence", _c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_double, _c_int,
+                                    _vp, _c_double, _c_int, _c_int, _c_int]),
+    ("slm_spots_sequence_read", _c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("slm_spots_fields", _c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("slm_spots_superpose", _c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
 ]
@@ -490,6 +493,7 @@ class Spots:
         self.max_traps, self.has_ain, self.max_loops = int(max_traps), bool(has_ain), int(max_loops)
         self.n_traps = 0
         self.loops = 0
+        self._seq = None  # (frames, traps, statistics rows per frame) of the last sequence
 
     def close(self) -> None:
         if getattr(self, "handle", None):
@@ -563,6 +567,62 @@ class Spots:
         check(self._lib.slm_spots_read(self.handle, ptr(out_phase), None if out_v is None else out_v.ctypes.data,
                                        ptr(out_stats), ptr(out_w)), "slm_spots_read")
         return out_phase, out_v, out_stats, out_w
+
+    def sequence(self, ys, xs, zs=None, intensity=None, weights0=None, loops_first: int = 30, loops: int = 4,
+                 tol: float = 0.0, resume: bool = False, mask=None, ct2pi=256, rule: int = QUANT_ASTYPE,
+                 frames: bool = True, phases: bool = False) -> None:
+        """slm_spots_sequence: a trajectory ys, xs, zs, intensity [F][batch][n_traps]
+        as one enqueued chain (frame f starts from frame f-1's unit field and
+        weights; tol > 0 stops a frame on the device once its uniformity is
+        <= tol). Returns once the chain is enqueued; sequence_read waits."""
+        y = np.ascontiguousarray(ys, dtype=np.float64)
+        if y.ndim < 2 or y.size == 0 or y.size % (y.shape[0] * self.batch):
+            raise ValueError(f"ys of shape {y.shape} is not [frames][batch {self.batch}][traps]")
+        f, n = y.shape[0], y.size // (y.shape[0] * self.batch)
+
+        def same(v, dtype, name):
+            if v is None:
+                return None
+            v = np.ascontiguousarray(v, dtype=dtype)
+            if v.size != y.size:
+                raise ValueError(f"{name} has {v.size} entries, ys {y.size}")
+            return v
+
+        x, z, i = same(xs, np.float64, "xs"), same(zs, np.float64, "zs"), same(intensity, np.float32, "intensity")
+        w0 = None
+        if weights0 is not None:
+            w0 = np.ascontiguousarray(weights0, dtype=np.float32)
+            if w0.size != self.batch * n:
+                raise ValueError(f"weights0 has {w0.size} entries for {self.batch} lists of {n} traps")
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(mask, dtype=np.float64)
+            if mk.shape != (self.height, self.width):
+                raise ValueError(f"the mask has shape {mk.shape}, the holograms {(self.height, self.width)}")
+        check(self._lib.slm_spots_sequence(self.handle, f, n, ptr(y), ptr(x), ptr(z), ptr(i), ptr(w0),
+                                           int(loops_first), int(loops), float(tol), int(bool(resume)), ptr(mk),
+                                           float(ct2pi), int(rule), int(bool(frames)), int(bool(phases))),
+              "slm_spots_sequence")
+        self.n_traps = n
+        self._seq = (f, n, max(int(loops_first), int(loops)))
+
+    def sequence_read(self, frames=True, phases=False, fields=True, stats=True, weights=True, iters=True):
+        """(frames uint8 [F][B][H][W], phases float32 [F][B][H][W], V complex128
+        [F][B][M], stats [F][B][max(loops_first, loops)][4] (rows past a frame's
+        iteration count are 0), weights float32 [F][B][M], iters int32 [F][B]) of
+        the last sequence; None where not asked for."""
+        f, n, rows = self._seq or (1, 1, 1)
+        fb = (f, self.batch)
+        out_f = np.empty(fb + (self.height, self.width), np.uint8) if frames else None
+        out_p = np.empty(fb + (self.height, self.width), np.float32) if phases else None
+        out_v = np.empty(fb + (n,), np.complex128) if fields else None
+        out_s = np.empty(fb + (rows, 4), np.float64) if stats else None
+        out_w = np.empty(fb + (n,), np.float32) if weights else None
+        out_i = np.empty(fb, np.int32) if iters else None
+        check(self._lib.slm_spots_sequence_read(self.handle, ptr(out_f), ptr(out_p),
+                                                None if out_v is None else out_v.ctypes.data, ptr(out_s), ptr(out_w),
+                                                ptr(out_i)), "slm_spots_sequence_read")
+        return out_f, out_p, out_v, out_s, out_w, out_i
 
     def info(self) -> dict:
         a = np.zeros(4, np.int32)

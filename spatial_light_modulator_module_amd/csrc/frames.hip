@@ -31,36 +31,18 @@
 #include <cstdint>
 #include <mutex>
 
+#include "quantize.hpp"
 #include "runtime.hpp"
 
 namespace {
 
 constexpr double kTwoPi = 6.283185307179586;  // 2 * np.pi as float64
 
-// Python / numpy float remainder: sign of the divisor (`%` on float64).
-__device__ __forceinline__ double py_mod(double a, double b) {
-    double r = fmod(a, b);
-    if (r != 0.0 && ((r < 0.0) != (b < 0.0))) r += b;
-    return r;
-}
-
-// numpy float64 -> uint8 astype: C truncation of the value (through int64,
-// so out-of-range levels wrap as they do on x86).
-__device__ __forceinline__ uint8_t astype_u8(double v) { return (uint8_t)(long long)v; }
-
-// PIL Image.fromarray(float64) is mode 'F' (float32); convert('L') clips to
-// [0, 255] and truncates (probed on Pillow 12.2, see tests/test_frames.py).
-__device__ __forceinline__ uint8_t pil_f_to_l(double v) {
-    const float f = (float)v;
-    if (!(f > 0.0f)) return 0;
-    if (f >= 255.0f) return 255;
-    return (uint8_t)(int)f;
-}
-
-__device__ __forceinline__ uint8_t quantize(double h, double m, double ct2pi, int rule) {
-    if (rule == SLM_QUANT_ASTYPE) return astype_u8(py_mod(h + m, kTwoPi) * ct2pi / kTwoPi);
-    return pil_f_to_l(py_mod(h + m, kTwoPi) / kTwoPi * ct2pi);
-}
+// py_mod, astype_u8, pil_f_to_l and quantize: quantize.hpp (shared with spots.hip)
+using slm::astype_u8;
+using slm::pil_f_to_l;
+using slm::py_mod;
+using slm::quantize;
 
 struct TransformParams {
     const double* in;  // [H][W] hologram or nullptr (zeros, the CLI's analytical case)

@@ -33,6 +33,15 @@
 // whole 256 B row segments and read back as 8 B per lane with a row stride of
 // 66 floats: lane (i, h) reads banks 2 i + 2 h (+1) mod 64 of step j's 4 j
 // offset, all 64 banks once per 32 lanes.
+//
+// Trap trajectories (slm_spots_sequence): F frames of a moving list as one
+// chain on the stream. Per frame one launch builds the four tables from
+// coordinates that went up once for all frames; the frame's iterations follow,
+// starting from the U and w the frame before left. One int per frame and
+// hologram is 0 while the frame runs and its iteration count afterwards: the
+// update kernel sets it (the fixed last iteration, or std(r) <= tol), later
+// launches of the frame return at once on it, and the superposition of that
+// very iteration also stores the float32 phase and the quantised uint8 frame.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +49,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "quantize.hpp"
 #include "runtime.hpp"
 
 namespace {
@@ -72,6 +82,16 @@ struct TableParams {
     int N, M, Mp, transposed;
 };
 
+// one table entry: float64 with the argument reduced first, rounded to complex64
+__device__ __forceinline__ float2 table_entry(int n, int N, double pos, double z) {
+    double t = (double)n * pos / (double)N;
+    t -= floor(t);  // the argument of the sine is reduced to [0, 2 pi) first
+    const double d = (double)n - 0.5 * (double)N;
+    double s, c;
+    sincos(kTwoPi * t + z * d * d, &s, &c);
+    return make_float2((float)c, (float)s);
+}
+
 __global__ void __launch_bounds__(256) spot_table_kernel(TableParams p) {
     const long long n_el = (long long)p.N * p.Mp;
     const int b = blockIdx.y;
@@ -85,16 +105,42 @@ __global__ void __launch_bounds__(256) spot_table_kernel(TableParams p) {
             m = (int)(i - (long long)n * p.Mp);
         }
         float2 v = make_float2(0.0f, 0.0f);
-        if (m < p.M) {
-            const double pos = p.pos[(size_t)b * p.M + m], z = p.z[(size_t)b * p.M + m];
-            double t = (double)n * pos / (double)p.N;
-            t -= floor(t);  // the argument of the sine is reduced to [0, 2 pi) first
-            const double d = (double)n - 0.5 * (double)p.N;
-            double s, c;
-            sincos(kTwoPi * t + z * d * d, &s, &c);
-            v = make_float2((float)c, (float)s);
-        }
+        if (m < p.M) v = table_entry(n, p.N, p.pos[(size_t)b * p.M + m], p.z[(size_t)b * p.M + m]);
         p.out[(size_t)b * n_el + i] = v;
+    }
+}
+
+// All four tables of one frame of a trajectory in one launch, from coordinates
+// that are already on the device: elements [0, H Mp) are Py, then PyT, Px and
+// PxT, each stored along its own fast index. grid = (blocks, batch).
+struct SeqTableParams {
+    const double *ys, *xs, *zs;  // this frame's [B][M]
+    float2 *py, *pyt, *px, *pxt;
+    int H, W, M, Mp;
+};
+
+__global__ void __launch_bounds__(256) spot_seq_tables_kernel(SeqTableParams p) {
+    const long long n_y = (long long)p.H * p.Mp, n_x = (long long)p.W * p.Mp, n_el = 2 * (n_y + n_x);
+    const int b = blockIdx.y;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n_el; i += (long long)gridDim.x * 256) {
+        const bool is_x = i >= 2 * n_y;
+        const long long n_t = is_x ? n_x : n_y;
+        long long j = is_x ? i - 2 * n_y : i;
+        const bool transposed = j >= n_t;
+        if (transposed) j -= n_t;
+        const int N = is_x ? p.W : p.H;
+        int n, m;
+        if (transposed) {
+            m = (int)(j / N);
+            n = (int)(j - (long long)m * N);
+        } else {
+            n = (int)(j / p.Mp);
+            m = (int)(j - (long long)n * p.Mp);
+        }
+        float2 v = make_float2(0.0f, 0.0f);
+        if (m < p.M) v = table_entry(n, N, (is_x ? p.xs : p.ys)[(size_t)b * p.M + m], p.zs[(size_t)b * p.M + m]);
+        float2* out = is_x ? (transposed ? p.pxt : p.px) : (transposed ? p.pyt : p.py);
+        out[(size_t)b * n_t + j] = v;
     }
 }
 
@@ -116,6 +162,7 @@ struct FieldsParams {
     double2* partial;   // [B][units][Mp]
     int H, W, Mp;
     int col_splits, cols_per_split, units;
+    const int* stop;    // [B] or nullptr: nonzero = this hologram's frame has ended (sequences)
 };
 
 // Four waves per workgroup; each wave takes 32 rows x cols_per_split columns of
@@ -127,6 +174,7 @@ struct FieldsParams {
 __global__ void __launch_bounds__(kFieldsThreads) spot_fields_kernel(FieldsParams p) {
     __shared__ float tiles[kWaves][kTile * kLdsStride];
     __shared__ double2 vsum[kWaves][kTile];
+    if (p.stop && p.stop[blockIdx.z] != 0) return;  // the whole workgroup, before any barrier
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
     float* tile = tiles[wave];
     const int unit = blockIdx.x, rg = unit / p.col_splits, cs = unit - rg * p.col_splits;
@@ -230,6 +278,11 @@ struct UpdateParams {
     double* stats;           // [B][max_loops][4], this iteration's row at + 4 it
     int M, Mp, units, max_loops, it;
     double feedback, inv_norm;  // inv_norm = 1 / (H W sum a^2)
+    // sequences (nullptr otherwise): stop[b] = 0 while hologram b's frame runs, then the number of
+    // iterations it took: set at iteration last_it, or earlier once std(r) <= tol (tol > 0)
+    int* stop;
+    int last_it;
+    double tol;
 };
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -266,6 +319,7 @@ __global__ void __launch_bounds__(kUpdThreads) spot_update_kernel(UpdateParams p
     __shared__ double2 fold[kUpdThreads];
     __shared__ double red[kUpdThreads / 64];
     const int b = blockIdx.x, t = threadIdx.x;
+    if (p.stop && p.stop[b] != 0) return;  // the whole workgroup, before any barrier
     const bool live = t < p.M;
 
     // fold the partials: group g takes units g, g + G, ...; the groups are then added in order
@@ -318,6 +372,7 @@ __global__ void __launch_bounds__(kUpdThreads) spot_update_kernel(UpdateParams p
         st[1] = sqrt(var_r);
         st[2] = min_r;
         st[3] = max_r;
+        if (p.stop && (p.it == p.last_it || (p.tol > 0.0 && sqrt(var_r) <= p.tol))) p.stop[b] = p.it + 1;
     }
 
     // weights: w *= (a_T / |V|)^p where |V| > 0, factor clamped to [2^-64, 2^64]; then mean 1
@@ -349,6 +404,14 @@ struct SuperposeParams {
     float2* u;          // [B][H][W]
     float* phase;       // [B][H][W] or nullptr (only the run's last iteration stores it)
     int H, W, M, Mp;
+    // sequences (stop = nullptr otherwise): iteration `it` of a frame is hologram b's last one when
+    // stop[b] == it + 1; only then are the phase and the quantised frame stored
+    const int* stop;     // [B]
+    int it;
+    uint8_t* frame;      // [B][H][W] or nullptr
+    const double* mask;  // [H][W] or nullptr
+    double ct2pi;
+    int rule;
 };
 
 // One wave per 32 x 32 output tile, four adjacent column tiles per workgroup (a
@@ -356,6 +419,12 @@ struct SuperposeParams {
 __global__ void __launch_bounds__(kFieldsThreads) spot_superpose_kernel(SuperposeParams p) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
     const int b = blockIdx.z, row0 = blockIdx.y * kTile, col0 = (blockIdx.x * kWaves + wave) * kTile;
+    bool last = true;
+    if (p.stop) {
+        const int n_it = p.stop[b];  // the same for the whole workgroup
+        if (n_it != 0 && n_it != p.it + 1) return;
+        last = n_it != 0;
+    }
     if (col0 >= p.W) return;  // no barriers below
     // rows / columns past the edge read the last valid line; their results are not stored
     const float2* py = p.pyt + (size_t)b * p.Mp * p.H + min(row0 + li, p.H - 1);
@@ -421,7 +490,13 @@ __global__ void __launch_bounds__(kFieldsThreads) spot_superpose_kernel(Superpos
             v = make_float2(sr * inv, si * inv);
         }
         p.u[base + (size_t)gr * p.W] = v;
-        if (p.phase) p.phase[base + (size_t)gr * p.W] = (float)atan2((double)sim[r], (double)sre[r]);
+        if (last && (p.phase || p.frame)) {
+            const float ph = (float)atan2((double)sim[r], (double)sre[r]);
+            if (p.phase) p.phase[base + (size_t)gr * p.W] = ph;
+            if (p.frame)
+                p.frame[base + (size_t)gr * p.W] =
+                    slm::quantize((double)ph, p.mask ? p.mask[(size_t)gr * p.W + gc] : 0.0, p.ct2pi, p.rule);
+        }
     }
 }
 
@@ -433,6 +508,30 @@ void dev_free(T*& p) {
     if (p) (void)hipFree(p);
     p = nullptr;
 }
+
+// a device buffer that only grows (the sequence buffers are sized at the call)
+template <typename T>
+struct Grown {
+    T* p = nullptr;
+    size_t cap = 0;  // bytes
+    int need(size_t bytes, hipStream_t st) {
+        if (bytes <= cap) return 0;
+        if (p) {
+            if (hipStreamSynchronize(st) != hipSuccess) return slm::fail(SLM_ERR_HIP, "hipStreamSynchronize failed");
+            (void)hipFree(p);
+        }
+        p = nullptr;
+        cap = 0;
+        RC(slm::dev_alloc(&p, bytes));
+        cap = bytes;
+        return 0;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
 
 }  // namespace
 
@@ -456,6 +555,19 @@ struct slm_spots {
     size_t partial_cap = 0;
     float2 *c = nullptr, *c0 = nullptr;
     std::vector<double> host_a_t;  // [B][M], for the default start
+    // the last sequence (slm_spots_sequence): per-frame slices, sized at the call
+    int seq_frames = 0, seq_traps = 0, seq_loops = 0;  // frames, traps and statistics rows per frame (0 = none yet)
+    bool seq_resumable = false, seq_has_frames = false, seq_has_phases = false;
+    Grown<double> seq_coords;  // ys, xs, zs [3][F][B][M]
+    Grown<double> seq_a_t;     // [F][B][Mp]
+    Grown<double> seq_w;       // [F + 1][B][Mp]: slice 0 is the start, slice f + 1 frame f's
+    Grown<double2> seq_v;      // [F][B][Mp]
+    Grown<double> seq_stats;   // [F][B][seq_loops][4]
+    Grown<int> seq_iters;      // [F][B]: the stop words, then the iteration counts
+    Grown<uint8_t> seq_out;    // [F][B][H][W] quantised frames
+    Grown<float> seq_phase;    // [F][B][H][W]
+    Grown<double> seq_mask;    // [H][W]
+    Grown<double> seq_w_last;  // [B][Mp]: the weights the last sequence ended with (resume)
 };
 
 namespace {
@@ -479,6 +591,16 @@ void spots_free(slm_spots* s) {
     dev_free(s->partial);
     dev_free(s->c);
     dev_free(s->c0);
+    s->seq_coords.release();
+    s->seq_a_t.release();
+    s->seq_w.release();
+    s->seq_v.release();
+    s->seq_stats.release();
+    s->seq_iters.release();
+    s->seq_out.release();
+    s->seq_phase.release();
+    s->seq_mask.release();
+    s->seq_w_last.release();
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -504,14 +626,43 @@ SuperposeParams superpose_params(slm_spots* s, const float2* c, float2* u, float
     return p;
 }
 
-int launch_superpose(slm_spots* s, const float2* c, float2* u, float* phase) {
+// what one frame of a sequence adds to the three launches of an iteration
+struct FrameSlices {
+    const double* a_t;   // [B][Mp]
+    const double* w_in;  // the previous frame's weights (iteration 0 reads them)
+    double* w;
+    double2* v;
+    double* stats;       // [B][stats_loops][4]
+    int stats_loops;
+    int* stop;           // [B]
+    int loops;           // this frame's iteration count at most
+    double tol;
+    float* phase;        // [B][H][W] or nullptr
+    uint8_t* frame;      // [B][H][W] or nullptr
+    const double* mask;
+    double ct2pi;
+    int rule;
+};
+
+int launch_superpose(slm_spots* s, const float2* c, float2* u, float* phase, const FrameSlices* fr = nullptr,
+                     int it = 0) {
     const dim3 grid((s->W + kWaves * kTile - 1) / (kWaves * kTile), (s->H + kTile - 1) / kTile, s->B);
-    hipLaunchKernelGGL(spot_superpose_kernel, grid, dim3(kFieldsThreads), 0, s->stream, superpose_params(s, c, u, phase));
+    SuperposeParams p = superpose_params(s, c, u, phase);
+    if (fr) {
+        p.phase = fr->phase;
+        p.stop = fr->stop;
+        p.it = it;
+        p.frame = fr->frame;
+        p.mask = fr->mask;
+        p.ct2pi = fr->ct2pi;
+        p.rule = fr->rule;
+    }
+    hipLaunchKernelGGL(spot_superpose_kernel, grid, dim3(kFieldsThreads), 0, s->stream, p);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int launch_fields(slm_spots* s, const float2* u) {
+int launch_fields(slm_spots* s, const float2* u, const int* stop = nullptr) {
     FieldsParams p{};
     p.u = u;
     p.ain = s->ain_set ? s->ain : nullptr;
@@ -524,13 +675,14 @@ int launch_fields(slm_spots* s, const float2* u) {
     p.col_splits = s->col_splits;
     p.cols_per_split = s->cols_per_split;
     p.units = s->units;
+    p.stop = stop;
     hipLaunchKernelGGL(spot_fields_kernel, dim3(s->units, s->Mp / kTile, s->B), dim3(kFieldsThreads), 0, s->stream,
                        p);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int launch_update(slm_spots* s, int it) {
+int launch_update(slm_spots* s, int it, const FrameSlices* fr = nullptr) {
     UpdateParams p{};
     p.partial = s->partial;
     p.a_t = s->a_t;
@@ -546,6 +698,17 @@ int launch_update(slm_spots* s, int it) {
     p.it = it;
     p.feedback = s->feedback;
     p.inv_norm = 1.0 / ((double)s->H * s->W * s->sum_a2);
+    if (fr) {
+        p.a_t = fr->a_t;
+        p.w_in = it == 0 ? fr->w_in : fr->w;
+        p.w_out = fr->w;
+        p.v = fr->v;
+        p.stats = fr->stats;
+        p.max_loops = fr->stats_loops;
+        p.stop = fr->stop;
+        p.last_it = fr->loops - 1;
+        p.tol = fr->tol;
+    }
     hipLaunchKernelGGL(spot_update_kernel, dim3(s->B), dim3(kUpdThreads), 0, s->stream, p);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -601,6 +764,7 @@ int run_loops(slm_spots* s, int loops, double* us_per_class) {
     if (loops < 1 || loops > s->max_loops)
         return fail(SLM_ERR_ARG, "loops %d outside 1 .. max_loops %d", loops, s->max_loops);
     RC(slm::ensure_device());
+    s->seq_resumable = false;  // the run overwrites the unit field a sequence left
     RC(default_start(s));
     Timer tm{{}, {}, s->stream, us_per_class != nullptr};
     for (int it = 0; it < loops; ++it) {
@@ -638,6 +802,23 @@ void plan_fields(slm_spots* s) {
     s->col_splits = (chunks + chunks_per - 1) / chunks_per;
     s->cols_per_split = chunks_per * kTile;
     s->units = (row_tiles + kWaves - 1) / kWaves * s->col_splits;
+}
+
+// a list of n_traps: the padded count, the cut of the fields product and its partial sums
+int set_list_size(slm_spots* s, int n_traps) {
+    s->M = n_traps;
+    s->Mp = padded_traps(n_traps);
+    s->has_run = false;
+    s->u0_valid = false;
+    plan_fields(s);
+    const size_t need = (size_t)s->B * s->units * s->Mp * sizeof(double2);
+    if (need > s->partial_cap) {
+        dev_free(s->partial);
+        s->partial_cap = 0;
+        RC(slm::dev_alloc(&s->partial, need));
+        s->partial_cap = need;
+    }
+    return 0;
 }
 
 int launch_table(slm_spots* s, const double* pos, const double* z, float2* out, int n, int transposed) {
@@ -717,18 +898,8 @@ int slm_spots_set_traps(slm_spots* s, int n_traps, const double* ys, const doubl
             return fail(SLM_ERR_ARG, "trap %zu: the intensity must be positive and finite", i);
     }
     RC(slm::ensure_device());
-    s->M = n_traps;
-    s->Mp = padded_traps(n_traps);
-    s->has_run = false;
-    s->u0_valid = false;
-    plan_fields(s);
-    const size_t need = (size_t)s->B * s->units * s->Mp * sizeof(double2);
-    if (need > s->partial_cap) {
-        dev_free(s->partial);
-        s->partial_cap = 0;
-        RC(slm::dev_alloc(&s->partial, need));
-        s->partial_cap = need;
-    }
+    s->seq_resumable = false;
+    RC(set_list_size(s, n_traps));
     std::vector<double> z0(n, 0.0);
     double *dy = s->coords, *dx = dy + n, *dz = dx + n;
     RC(up(s, dy, ys, n * sizeof(double)));
@@ -763,6 +934,7 @@ int slm_spots_set_ain(slm_spots* s, const float* ain) {
     }
     if (!(sum > 0.0)) return fail(SLM_ERR_ARG, "a_in is zero everywhere");
     RC(slm::ensure_device());
+    s->seq_resumable = false;
     RC(up(s, s->ain, ain, holo * sizeof(float)));
     s->sum_a2 = sum;
     s->ain_set = true;
@@ -772,6 +944,7 @@ int slm_spots_set_ain(slm_spots* s, const float* ain) {
 int slm_spots_set_phase(slm_spots* s, const float* phase) {
     if (!s) return fail(SLM_ERR_ARG, "null spots handle");
     RC(slm::ensure_device());
+    s->seq_resumable = false;
     s->u0_valid = false;
     s->custom_phase = phase != nullptr;
     if (!phase) return 0;
@@ -788,6 +961,7 @@ int slm_spots_set_phase(slm_spots* s, const float* phase) {
 int slm_spots_set_weights(slm_spots* s, const float* weights) {
     if (!s) return fail(SLM_ERR_ARG, "null spots handle");
     if (!s->M) return fail(SLM_ERR_STATE, "slm_spots_set_weights before slm_spots_set_traps");
+    s->seq_resumable = false;
     std::vector<double> w((size_t)s->B * s->Mp, 1.0);
     if (weights)
         for (int b = 0; b < s->B; ++b)
@@ -805,6 +979,7 @@ int slm_spots_set_feedback(slm_spots* s, float feedback) {
     if (!s) return fail(SLM_ERR_ARG, "null spots handle");
     if (!(feedback >= 0.0f) || !std::isfinite(feedback))
         return fail(SLM_ERR_ARG, "feedback must be finite and >= 0, got %g", (double)feedback);
+    s->seq_resumable = false;
     s->feedback = feedback;
     return 0;
 }
@@ -845,6 +1020,172 @@ int slm_spots_read(slm_spots* s, float* phase, double* fields, double* stats, fl
         for (int b = 0; b < s->B; ++b)
             for (int m = 0; m < s->M; ++m) weights[(size_t)b * s->M + m] = (float)w[(size_t)b * s->Mp + m];
     }
+    return 0;
+}
+
+int slm_spots_sequence(slm_spots* s, int n_frames, int n_traps, const double* ys, const double* xs, const double* zs,
+                       const float* intensity, const float* weights0, int loops_first, int loops, double tol,
+                       int resume, const double* mask, double ct2pi, int rule, int want_frames, int want_phases) {
+    if (!s || !ys || !xs) return fail(SLM_ERR_ARG, "null argument");
+    if (n_frames < 1) return fail(SLM_ERR_ARG, "%d frames: a sequence has at least one", n_frames);
+    if (n_traps < 1 || n_traps > s->max_traps)
+        return fail(SLM_ERR_ARG, "%d traps outside 1 .. max_traps %d", n_traps, s->max_traps);
+    if (loops_first < 1 || loops_first > s->max_loops || loops < 1 || loops > s->max_loops)
+        return fail(SLM_ERR_ARG, "loops_first %d and loops %d must lie in 1 .. max_loops %d", loops_first, loops,
+                    s->max_loops);
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(SLM_ERR_ARG, "tol must be finite and >= 0, got %g", tol);
+    if (rule != SLM_QUANT_ASTYPE && rule != SLM_QUANT_PIL) return fail(SLM_ERR_ARG, "unknown rule %d", rule);
+    if (!(ct2pi > 0.0) || !std::isfinite(ct2pi))
+        return fail(SLM_ERR_ARG, "ct2pi must be finite and positive, got %g", ct2pi);
+    if (resume && weights0) return fail(SLM_ERR_ARG, "a resumed sequence takes its weights from the previous one");
+    const size_t bm_in = (size_t)s->B * n_traps, n = (size_t)n_frames * bm_in;
+    for (size_t i = 0; i < n; ++i) {
+        if (!std::isfinite(ys[i]) || !std::isfinite(xs[i]) || (zs && !std::isfinite(zs[i])))
+            return fail(SLM_ERR_ARG, "trap %zu has a non-finite coordinate", i);
+        if (intensity && !(intensity[i] > 0.0f && std::isfinite(intensity[i])))
+            return fail(SLM_ERR_ARG, "trap %zu: the intensity must be positive and finite", i);
+    }
+    if (weights0)
+        for (size_t i = 0; i < bm_in; ++i)
+            if (!(weights0[i] > 0.0f && std::isfinite(weights0[i])))
+                return fail(SLM_ERR_ARG, "weight %zu is not positive and finite", i);
+    if (s->has_ain && !s->ain_set) return fail(SLM_ERR_STATE, "slm_spots_sequence before slm_spots_set_ain");
+    if (resume && !(s->seq_resumable && s->seq_traps == n_traps))
+        return fail(SLM_ERR_STATE, "resume needs a previous sequence of %d traps with no set_* or run since", n_traps);
+    RC(slm::ensure_device());
+
+    // ---- buffers, sized for this call ----
+    const int mp = padded_traps(n_traps), stats_loops = std::max(loops_first, loops);
+    const size_t bmp = (size_t)s->B * mp, holo = (size_t)s->H * s->W, F = (size_t)n_frames;
+    s->seq_frames = 0;  // nothing to read, and nothing to resume from, if this call fails half way
+    s->seq_resumable = false;
+    RC(s->seq_coords.need(3 * n * sizeof(double), s->stream));
+    RC(s->seq_a_t.need(F * bmp * sizeof(double), s->stream));
+    RC(s->seq_w.need((F + 1) * bmp * sizeof(double), s->stream));
+    RC(s->seq_v.need(F * bmp * sizeof(double2), s->stream));
+    RC(s->seq_stats.need(F * s->B * stats_loops * 4 * sizeof(double), s->stream));
+    RC(s->seq_iters.need(F * s->B * sizeof(int), s->stream));
+    RC(s->seq_w_last.need((size_t)s->B * padded_traps(s->max_traps) * sizeof(double), s->stream));
+    if (want_frames) RC(s->seq_out.need(F * s->B * holo, s->stream));
+    if (want_frames && mask) RC(s->seq_mask.need(holo * sizeof(double), s->stream));
+    if (want_phases) RC(s->seq_phase.need(F * s->B * holo * sizeof(float), s->stream));
+    RC(set_list_size(s, n_traps));
+
+    // ---- everything the chain reads goes up once ----
+    double *dy = s->seq_coords.p, *dx = dy + n, *dz = dx + n;
+    RC(up(s, dy, ys, n * sizeof(double)));
+    RC(up(s, dx, xs, n * sizeof(double)));
+    if (zs)
+        RC(up(s, dz, zs, n * sizeof(double)));
+    else
+        HIP_TRY(hipMemsetAsync(dz, 0, n * sizeof(double), s->stream));
+    std::vector<double> a_t(F * bmp, 1.0);
+    if (intensity)
+        for (size_t fb = 0; fb < F * s->B; ++fb)
+            for (int m = 0; m < n_traps; ++m) a_t[fb * mp + m] = std::sqrt((double)intensity[fb * n_traps + m]);
+    RC(up(s, s->seq_a_t.p, a_t.data(), a_t.size() * sizeof(double)));
+    if (resume) {
+        HIP_TRY(hipMemcpyAsync(s->seq_w.p, s->seq_w_last.p, bmp * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
+    } else {
+        std::vector<double> w(bmp, 1.0);
+        if (weights0)
+            for (int b = 0; b < s->B; ++b)
+                for (int m = 0; m < n_traps; ++m) w[(size_t)b * mp + m] = weights0[(size_t)b * n_traps + m];
+        RC(up(s, s->seq_w.p, w.data(), w.size() * sizeof(double)));
+    }
+    if (want_frames && mask) RC(up(s, s->seq_mask.p, mask, holo * sizeof(double)));
+    // the handle's own list becomes the last frame's, its weights ones (the chain reads neither)
+    std::vector<double> ones(bmp, 1.0);
+    RC(up(s, s->a_t, a_t.data() + (F - 1) * bmp, bmp * sizeof(double)));
+    RC(up(s, s->w0, ones.data(), ones.size() * sizeof(double)));
+    // the stop words start at 0 and the statistics rows a frame does not reach stay 0
+    HIP_TRY(hipMemsetAsync(s->seq_iters.p, 0, F * s->B * sizeof(int), s->stream));
+    HIP_TRY(hipMemsetAsync(s->seq_stats.p, 0, F * s->B * stats_loops * 4 * sizeof(double), s->stream));
+
+    // ---- the chain: per frame one table launch, then its iterations ----
+    auto host_a_t = [&](size_t f) {
+        s->host_a_t.assign(bm_in, 1.0);
+        for (int b = 0; b < s->B; ++b)
+            for (int m = 0; m < n_traps; ++m)
+                s->host_a_t[(size_t)b * n_traps + m] = a_t[(f * s->B + b) * mp + m];
+    };
+    for (size_t f = 0; f < F; ++f) {
+        SeqTableParams tp{dy + f * bm_in, dx + f * bm_in, dz + f * bm_in, s->py, s->pyt, s->px, s->pxt, s->H, s->W,
+                          n_traps, mp};
+        hipLaunchKernelGGL(spot_seq_tables_kernel, dim3(grid_for(2LL * (s->H + s->W) * mp), s->B), dim3(256), 0,
+                           s->stream, tp);
+        HIP_TRY(hipGetLastError());
+        const bool first = f == 0 && !resume;
+        if (first) {
+            host_a_t(0);
+            RC(default_start(s));
+        }
+        FrameSlices fr{};
+        fr.a_t = s->seq_a_t.p + f * bmp;
+        fr.w_in = s->seq_w.p + f * bmp;
+        fr.w = s->seq_w.p + (f + 1) * bmp;
+        fr.v = s->seq_v.p + f * bmp;
+        fr.stats = s->seq_stats.p + f * s->B * stats_loops * 4;
+        fr.stats_loops = stats_loops;
+        fr.stop = s->seq_iters.p + f * s->B;
+        fr.loops = first ? loops_first : loops;
+        fr.tol = tol;
+        fr.phase = want_phases ? s->seq_phase.p + f * s->B * holo : nullptr;
+        fr.frame = want_frames ? s->seq_out.p + f * s->B * holo : nullptr;
+        fr.mask = want_frames && mask ? s->seq_mask.p : nullptr;
+        fr.ct2pi = ct2pi;
+        fr.rule = rule;
+        for (int it = 0; it < fr.loops; ++it) {
+            RC(launch_fields(s, first && it == 0 ? s->u0 : s->u, fr.stop));
+            RC(launch_update(s, it, &fr));
+            RC(launch_superpose(s, s->c, s->u, nullptr, &fr, it));
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(s->seq_w_last.p, s->seq_w.p + F * bmp, bmp * sizeof(double), hipMemcpyDeviceToDevice,
+                           s->stream));
+
+    // ---- the handle is as after slm_spots_set_traps with the last list ----
+    host_a_t(F - 1);
+    s->u0_valid = false;
+    s->has_run = false;
+    s->seq_frames = n_frames;
+    s->seq_traps = n_traps;
+    s->seq_loops = stats_loops;
+    s->seq_has_frames = want_frames != 0;
+    s->seq_has_phases = want_phases != 0;
+    s->seq_resumable = true;
+    return 0;
+}
+
+int slm_spots_sequence_read(slm_spots* s, unsigned char* frames, float* phases, double* fields, double* stats,
+                            float* weights, int* iters) {
+    if (!s) return fail(SLM_ERR_ARG, "null spots handle");
+    if (!s->seq_frames) return fail(SLM_ERR_STATE, "slm_spots_sequence_read before a sequence");
+    if (frames && !s->seq_has_frames) return fail(SLM_ERR_STATE, "the sequence was run without frames");
+    if (phases && !s->seq_has_phases) return fail(SLM_ERR_STATE, "the sequence was run without phases");
+    RC(slm::ensure_device());
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    const int mt = s->seq_traps, mp = padded_traps(mt);
+    const size_t F = (size_t)s->seq_frames, fb = F * s->B, holo = (size_t)s->H * s->W;
+    if (frames) RC(down(s, frames, s->seq_out.p, fb * holo));
+    if (phases) RC(down(s, phases, s->seq_phase.p, fb * holo * sizeof(float)));
+    if (fields) {
+        std::vector<double2> v(fb * mp);
+        RC(down(s, v.data(), s->seq_v.p, v.size() * sizeof(double2)));
+        for (size_t k = 0; k < fb; ++k)
+            for (int m = 0; m < mt; ++m) {
+                fields[2 * (k * mt + m)] = v[k * mp + m].x;
+                fields[2 * (k * mt + m) + 1] = v[k * mp + m].y;
+            }
+    }
+    if (stats) RC(down(s, stats, s->seq_stats.p, fb * s->seq_loops * 4 * sizeof(double)));
+    if (weights) {
+        std::vector<double> w(fb * mp);
+        RC(down(s, w.data(), s->seq_w.p + (size_t)s->B * mp, w.size() * sizeof(double)));
+        for (size_t k = 0; k < fb; ++k)
+            for (int m = 0; m < mt; ++m) weights[k * mt + m] = (float)w[k * mp + m];
+    }
+    if (iters) RC(down(s, iters, s->seq_iters.p, fb * sizeof(int)));
     return 0;
 }
 

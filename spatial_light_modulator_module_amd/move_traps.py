@@ -16,6 +16,13 @@ DESIGN.md section 7).
   the hologram of a whole list of traps (fractional positions, a defocus per
   trap, uniform or chosen intensities) by spot-based weighted GS on the GPU
   (slm_spots_*), on any panel shape.
+* ``trap_array_sequence`` — no reference counterpart either: a whole
+  trajectory of such a list (F frames of the same M traps, moved) as one chain
+  on the device (slm_spots_sequence). Each frame starts from the previous
+  frame's field and weights, may stop once its uniformity meets a tolerance,
+  and leaves the device as the uint8 SLM frame. The reference's route to moving
+  traps (generate_traps_image_sequence.py, then GS per rasterised frame) rounds
+  the positions to whole pixels; this one keeps them fractional.
 """
 from __future__ import annotations
 
@@ -149,6 +156,100 @@ def trap_array_frame(shape, ys, xs, zs=None, intensity=None, loops=30, feedback=
                                                       initial_phase, initial_weights)
     frame = hologram_frame(holo, mask, mask_flag and mask is not None, ct2pi)
     return holo, frame, inten, stats, weights
+
+
+SequenceResult = collections.namedtuple("SequenceResult", "frames holograms intensities stats iters weights")
+SequenceResult.__doc__ = """What trap_array_sequence returns, every field with a leading [F] (one
+trajectory) or [F][B] (a batch): frames uint8 [H][W], holograms float64 [H][W]
+or None, intensities |V_m|^2 [M], stats [max(loops_first, loops)][4] (rows past
+iters are 0), iters (iterations each frame ran), weights [M]."""
+
+
+def _sequence_arrays(ys, xs, zs, intensity, initial_weights):
+    """The trajectory as [F][B][M] arrays (None where not given), and whether
+    it was one trajectory [F][M]; ValueError on any shape mismatch."""
+    y = np.asarray(ys, dtype=np.float64)
+    if y.ndim not in (2, 3) or y.size == 0:
+        raise ValueError(f"ys has shape {y.shape}: a trajectory is [F][M], a batch of them [F][B][M]")
+    single = y.ndim == 2
+    if single:
+        y = y[:, None, :]
+
+    def like(v, name, dtype=np.float64):
+        if v is None:
+            return None
+        v = np.asarray(v, dtype=dtype)
+        if single and v.ndim == 2:
+            v = v[:, None, :]
+        if v.shape != y.shape:
+            raise ValueError(f"{name} has shape {np.shape(v)}, the trajectory {np.shape(ys)}")
+        return v
+
+    x = like(xs, "xs")
+    if x is None:
+        raise ValueError("xs is required")
+    z, inten = like(zs, "zs"), like(intensity, "intensity")
+    w0 = None
+    if initial_weights is not None:
+        w0 = np.atleast_2d(np.asarray(initial_weights, dtype=np.float64))
+        if w0.shape != y.shape[1:]:
+            raise ValueError(f"initial_weights has shape {w0.shape}, the trap lists {y.shape[1:]}")
+    return y, x, z, inten, w0, single
+
+
+def trap_array_sequence(shape, ys, xs, zs=None, intensity=None, loops_first=30, loops=4, tol=0.0, feedback=1.0,
+                        ain=None, initial_phase=None, initial_weights=None, mask=None, mask_flag: bool = True,
+                        ct2pi=256, holograms=False, resume=False) -> SequenceResult:
+    """A trajectory of a trap list as one chain on the device
+    (slm_spots_sequence): ys, xs, zs, intensity are [F][M], or [F][B][M] for B
+    trajectories at once; trap m of frame f is trap m of frame f-1, moved.
+    Frame 0 runs at most loops_first iterations from initial_phase (or the
+    default start) and initial_weights (or ones); every later frame at most
+    `loops` from the field and weights the frame before ended with. With
+    tol > 0 a frame ends with the first iteration whose incoming uniformity
+    std(r) is <= tol. Each frame is quantised on the device as hologram_frame
+    does. resume=True continues the last sequence of the cached handle for this
+    shape and trap count: its frame 0 is an ordinary later frame, feedback and
+    a_in stay the handle's, and initial_phase / initial_weights must be None.
+    Returns a SequenceResult; holograms (float64, as update_hologram's) only
+    with holograms=True."""
+    h, w = int(shape[0]), int(shape[1])
+    y, x, z, inten, w0, single = _sequence_arrays(ys, xs, zs, intensity, initial_weights)
+    f, b, m = y.shape
+    if initial_phase is not None and np.size(initial_phase) != b * h * w:
+        raise ValueError(f"initial_phase has {np.size(initial_phase)} entries, {b} holograms of {h} x {w} need "
+                         f"{b * h * w}")
+    use_mask = mask is not None and mask_flag
+    if use_mask and np.shape(mask) != (h, w):
+        raise ValueError(f"the mask has shape {np.shape(mask)}, the holograms {(h, w)}")
+    n_loops = max(int(loops_first), int(loops))
+    if resume:
+        if initial_phase is not None or initial_weights is not None:
+            raise ValueError("a resumed sequence starts from the previous one: no initial_phase or initial_weights")
+        max_traps = max(min(_lib.SPOTS_MAX_TRAPS, -(-m // 32) * 32), m)
+        sp = _SPOTS.get((b, h, w, max_traps, ain is not None))
+        if sp is None or sp._seq is None or sp._seq[1] != m or sp.max_loops < n_loops:
+            raise ValueError("resume=True needs a cached handle that holds a sequence of this shape and trap count")
+    else:
+        sp = _get_spots(b, h, w, m, ain is not None, n_loops)
+        if ain is not None:
+            sp.set_ain(ain)
+        sp.set_feedback(feedback)
+        sp.set_phase(None if initial_phase is None else np.asarray(initial_phase).reshape(b, h, w))
+    try:
+        sp.sequence(y, x, z, inten, w0, loops_first, loops, tol, resume, mask if use_mask else None, ct2pi,
+                    _lib.QUANT_ASTYPE, frames=True, phases=bool(holograms))
+    except _lib.SlmError as e:
+        if resume and e.code == _lib.ERR_STATE:
+            raise ValueError(f"resume=True: {e}") from e
+        raise
+    frames, phases, v, stats, weights, iters = sp.sequence_read(phases=bool(holograms))
+    holo = phases.astype(np.float64) if holograms else None
+    inten_out = v.real ** 2 + v.imag ** 2
+    if single:
+        return SequenceResult(frames[:, 0], None if holo is None else holo[:, 0], inten_out[:, 0], stats[:, 0],
+                              iters[:, 0], weights[:, 0])
+    return SequenceResult(frames, holo, inten_out, stats, iters, weights)
 
 
 def trap_frame(shape, coords, which, mask=None, mask_flag: bool = True, ct2pi=256):
