@@ -42,6 +42,11 @@
 // update kernel sets it (the fixed last iteration, or std(r) <= tol), later
 // launches of the frame return at once on it, and the superposition of that
 // very iteration also stores the float32 phase and the quantised uint8 frame.
+//
+// Host side: every device buffer is a DevBuf; a list's four tables are one
+// launch (launch_tables), for slm_spots_set_traps and for a frame alike; and
+// run_frame issues the iterations a Frame describes: a run is the handle's own
+// buffers without a stop word (own_frame), a trajectory one slice per frame.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -75,13 +80,6 @@ __device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
 }
 
 // ---- tables ---------------------------------------------------------------
-struct TableParams {
-    const double* pos;  // [B][M] trap coordinate along this axis
-    const double* z;    // [B][M] defocus
-    float2* out;        // [B][N][Mp] or (transposed) [B][Mp][N]
-    int N, M, Mp, transposed;
-};
-
 // one table entry: float64 with the argument reduced first, rounded to complex64
 __device__ __forceinline__ float2 table_entry(int n, int N, double pos, double z) {
     double t = (double)n * pos / (double)N;
@@ -92,29 +90,12 @@ __device__ __forceinline__ float2 table_entry(int n, int N, double pos, double z
     return make_float2((float)c, (float)s);
 }
 
-__global__ void __launch_bounds__(256) spot_table_kernel(TableParams p) {
-    const long long n_el = (long long)p.N * p.Mp;
-    const int b = blockIdx.y;
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n_el; i += (long long)gridDim.x * 256) {
-        int n, m;
-        if (p.transposed) {
-            m = (int)(i / p.N);
-            n = (int)(i - (long long)m * p.N);
-        } else {
-            n = (int)(i / p.Mp);
-            m = (int)(i - (long long)n * p.Mp);
-        }
-        float2 v = make_float2(0.0f, 0.0f);
-        if (m < p.M) v = table_entry(n, p.N, p.pos[(size_t)b * p.M + m], p.z[(size_t)b * p.M + m]);
-        p.out[(size_t)b * n_el + i] = v;
-    }
-}
-
-// All four tables of one frame of a trajectory in one launch, from coordinates
-// that are already on the device: elements [0, H Mp) are Py, then PyT, Px and
-// PxT, each stored along its own fast index. grid = (blocks, batch).
+// All four tables of one list (a handle's, or one frame's of a trajectory) in
+// one launch, from coordinates that are already on the device: elements
+// [0, H Mp) are Py, then PyT, Px and PxT, each stored along its own fast index.
+// grid = (blocks, batch).
 struct SeqTableParams {
-    const double *ys, *xs, *zs;  // this frame's [B][M]
+    const double *ys, *xs, *zs;  // this list's [B][M]
     float2 *py, *pyt, *px, *pxt;
     int H, W, M, Mp;
 };
@@ -503,17 +484,19 @@ __global__ void __launch_bounds__(kFieldsThreads) spot_superpose_kernel(Superpos
 int grid_for(long long n) { return (int)std::min<long long>(8192, (n + 255) / 256); }
 int padded_traps(int m) { return (m + kTile - 1) / kTile * kTile; }
 
+// an owning device buffer that only grows (non-copyable, freed with its owner)
 template <typename T>
-void dev_free(T*& p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-// a device buffer that only grows (the sequence buffers are sized at the call)
-template <typename T>
-struct Grown {
+struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;  // bytes
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    // at least `bytes`; work on `st` may still read a live buffer, so the stream is waited for before
+    // it is freed. The buffer is empty if the allocation fails.
     int need(size_t bytes, hipStream_t st) {
         if (bytes <= cap) return 0;
         if (p) {
@@ -525,11 +508,6 @@ struct Grown {
         RC(slm::dev_alloc(&p, bytes));
         cap = bytes;
         return 0;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
     }
 };
 
@@ -545,62 +523,34 @@ struct slm_spots {
     bool ain_set = false, custom_phase = false, u0_valid = false, has_run = false;
     int last_loops = 0;
     hipStream_t stream = nullptr;
-    float* ain = nullptr;
-    float2 *u0 = nullptr, *u = nullptr;  // the start (runs read it, never write it) and the state
-    float* phase = nullptr;
-    float2 *py = nullptr, *px = nullptr, *pyt = nullptr, *pxt = nullptr;
-    double *coords = nullptr;  // ys, xs, zs [3][B][max_traps]
-    double *a_t = nullptr, *w0 = nullptr, *w = nullptr, *stats = nullptr;
-    double2 *v = nullptr, *partial = nullptr;
-    size_t partial_cap = 0;
-    float2 *c = nullptr, *c0 = nullptr;
+    DevBuf<float> ain;
+    DevBuf<float2> u0, u;  // the start (runs read it, never write it) and the state
+    DevBuf<float> phase;
+    DevBuf<float2> py, px, pyt, pxt;
+    DevBuf<double> coords;  // ys, xs, zs [3][B][M]
+    DevBuf<double> a_t, w0, w, stats;
+    DevBuf<double2> v, partial;  // partial is sized for the list (set_list_size)
+    DevBuf<float2> c, c0;
     std::vector<double> host_a_t;  // [B][M], for the default start
     // the last sequence (slm_spots_sequence): per-frame slices, sized at the call
     int seq_frames = 0, seq_traps = 0, seq_loops = 0;  // frames, traps and statistics rows per frame (0 = none yet)
     bool seq_resumable = false, seq_has_frames = false, seq_has_phases = false;
-    Grown<double> seq_coords;  // ys, xs, zs [3][F][B][M]
-    Grown<double> seq_a_t;     // [F][B][Mp]
-    Grown<double> seq_w;       // [F + 1][B][Mp]: slice 0 is the start, slice f + 1 frame f's
-    Grown<double2> seq_v;      // [F][B][Mp]
-    Grown<double> seq_stats;   // [F][B][seq_loops][4]
-    Grown<int> seq_iters;      // [F][B]: the stop words, then the iteration counts
-    Grown<uint8_t> seq_out;    // [F][B][H][W] quantised frames
-    Grown<float> seq_phase;    // [F][B][H][W]
-    Grown<double> seq_mask;    // [H][W]
-    Grown<double> seq_w_last;  // [B][Mp]: the weights the last sequence ended with (resume)
+    DevBuf<double> seq_coords;  // ys, xs, zs [3][F][B][M]
+    DevBuf<double> seq_a_t;     // [F][B][Mp]
+    DevBuf<double> seq_w;       // [F + 1][B][Mp]: slice 0 is the start, slice f + 1 frame f's
+    DevBuf<double2> seq_v;      // [F][B][Mp]
+    DevBuf<double> seq_stats;   // [F][B][seq_loops][4]
+    DevBuf<int> seq_iters;      // [F][B]: the stop words, then the iteration counts
+    DevBuf<uint8_t> seq_out;    // [F][B][H][W] quantised frames
+    DevBuf<float> seq_phase;    // [F][B][H][W]
+    DevBuf<double> seq_mask;    // [H][W]
+    DevBuf<double> seq_w_last;  // [B][Mp]: the weights the last sequence ended with (resume)
 };
 
 namespace {
 
 void spots_free(slm_spots* s) {
     if (!s) return;
-    dev_free(s->ain);
-    dev_free(s->u0);
-    dev_free(s->u);
-    dev_free(s->phase);
-    dev_free(s->py);
-    dev_free(s->px);
-    dev_free(s->pyt);
-    dev_free(s->pxt);
-    dev_free(s->coords);
-    dev_free(s->a_t);
-    dev_free(s->w0);
-    dev_free(s->w);
-    dev_free(s->stats);
-    dev_free(s->v);
-    dev_free(s->partial);
-    dev_free(s->c);
-    dev_free(s->c0);
-    s->seq_coords.release();
-    s->seq_a_t.release();
-    s->seq_w.release();
-    s->seq_v.release();
-    s->seq_stats.release();
-    s->seq_iters.release();
-    s->seq_out.release();
-    s->seq_phase.release();
-    s->seq_mask.release();
-    s->seq_w_last.release();
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
@@ -612,30 +562,90 @@ int down(slm_spots* s, void* dst, const void* src, size_t bytes) {
     return slm::copy_sync(dst, src, bytes, hipMemcpyDeviceToHost, s->stream);
 }
 
-SuperposeParams superpose_params(slm_spots* s, const float2* c, float2* u, float* phase) {
-    SuperposeParams p{};
-    p.pyt = s->pyt;
-    p.pxt = s->pxt;
-    p.c = c;
-    p.u = u;
-    p.phase = phase;
-    p.H = s->H;
-    p.W = s->W;
-    p.M = s->M;
-    p.Mp = s->Mp;
-    return p;
+// ---- host helpers shared by the list and the sequence entry points --------
+// `n` traps (all holograms, all frames): finite coordinates, positive finite intensities
+int check_traps(size_t n, const double* ys, const double* xs, const double* zs, const float* intensity) {
+    for (size_t i = 0; i < n; ++i) {
+        if (!std::isfinite(ys[i]) || !std::isfinite(xs[i]) || (zs && !std::isfinite(zs[i])))
+            return fail(SLM_ERR_ARG, "trap %zu has a non-finite coordinate", i);
+        if (intensity && !(intensity[i] > 0.0f && std::isfinite(intensity[i])))
+            return fail(SLM_ERR_ARG, "trap %zu: the intensity must be positive and finite", i);
+    }
+    return 0;
 }
 
-// what one frame of a sequence adds to the three launches of an iteration
-struct FrameSlices {
+// start weights [B][M] or nullptr (= ones)
+int check_weights(const slm_spots* s, int M, const float* weights) {
+    for (size_t i = 0; weights && i < (size_t)s->B * M; ++i)
+        if (!(weights[i] > 0.0f && std::isfinite(weights[i])))
+            return fail(SLM_ERR_ARG, "weight %d of hologram %d is not positive and finite", (int)(i % M), (int)(i / M));
+    return 0;
+}
+
+// [rows][M] -> [rows][Mp]: entry (r, m) is at(r M + m), the padding is `fill`
+template <typename T, typename At>
+std::vector<T> pad(size_t rows, int M, int Mp, T fill, At at) {
+    std::vector<T> out(rows * Mp, fill);
+    for (size_t r = 0; r < rows; ++r)
+        for (int m = 0; m < M; ++m) out[r * Mp + m] = at(r * M + m);
+    return out;
+}
+
+// device V [rows][Mp] -> fields [rows][M][2]
+int read_fields(slm_spots* s, const double2* dev, size_t rows, int M, int Mp, double* fields) {
+    std::vector<double2> v(rows * Mp);
+    RC(down(s, v.data(), dev, v.size() * sizeof(double2)));
+    for (size_t r = 0; r < rows; ++r)
+        for (int m = 0; m < M; ++m) {
+            fields[2 * (r * M + m)] = v[r * Mp + m].x;
+            fields[2 * (r * M + m) + 1] = v[r * Mp + m].y;
+        }
+    return 0;
+}
+
+// device w [rows][Mp] float64 -> weights [rows][M] float32
+int read_weights(slm_spots* s, const double* dev, size_t rows, int M, int Mp, float* weights) {
+    std::vector<double> w(rows * Mp);
+    RC(down(s, w.data(), dev, w.size() * sizeof(double)));
+    for (size_t r = 0; r < rows; ++r)
+        for (int m = 0; m < M; ++m) weights[r * M + m] = (float)w[r * Mp + m];
+    return 0;
+}
+
+// the current list's a_T on the host, from its padded form [B][Mp]
+void refill_host_a_t(slm_spots* s, const double* a_t) {
+    s->host_a_t.resize((size_t)s->B * s->M);
+    for (int b = 0; b < s->B; ++b) std::copy_n(a_t + (size_t)b * s->Mp, s->M, &s->host_a_t[(size_t)b * s->M]);
+}
+
+// ys, xs, zs (nullptr = 0) of n traps each to dst[0 .. 3 n)
+int upload_coords(slm_spots* s, double* dst, size_t n, const double* ys, const double* xs, const double* zs) {
+    RC(up(s, dst, ys, n * sizeof(double)));
+    RC(up(s, dst + n, xs, n * sizeof(double)));
+    if (zs) return up(s, dst + 2 * n, zs, n * sizeof(double));
+    HIP_TRY(hipMemsetAsync(dst + 2 * n, 0, n * sizeof(double), s->stream));
+    return 0;
+}
+
+// weights [B][M] of the current list, or nullptr = ones, to dst [B][Mp]
+int upload_weights(slm_spots* s, double* dst, const float* weights) {
+    const std::vector<double> w =
+        pad(s->B, s->M, s->Mp, 1.0, [&](size_t i) { return weights ? (double)weights[i] : 1.0; });
+    return up(s, dst, w.data(), w.size() * sizeof(double));
+}
+
+// ---- launches -------------------------------------------------------------
+// Where one frame's a_T, weights, V, statistics, stop word and outputs live: a
+// slice of the sequence buffers, or (own_frame) the handle's buffers for a run.
+struct Frame {
     const double* a_t;   // [B][Mp]
-    const double* w_in;  // the previous frame's weights (iteration 0 reads them)
+    const double* w_in;  // the weights iteration 0 reads: the start, or the previous frame's
     double* w;
     double2* v;
     double* stats;       // [B][stats_loops][4]
     int stats_loops;
-    int* stop;           // [B]
-    int loops;           // this frame's iteration count at most
+    int* stop;           // [B], or nullptr: all `loops` iterations run and only the last stores the phase
+    int loops;           // this frame's iteration count (at most, with a stop word)
     double tol;
     float* phase;        // [B][H][W] or nullptr
     uint8_t* frame;      // [B][H][W] or nullptr
@@ -644,72 +654,47 @@ struct FrameSlices {
     int rule;
 };
 
-int launch_superpose(slm_spots* s, const float2* c, float2* u, float* phase, const FrameSlices* fr = nullptr,
-                     int it = 0) {
-    const dim3 grid((s->W + kWaves * kTile - 1) / (kWaves * kTile), (s->H + kTile - 1) / kTile, s->B);
-    SuperposeParams p = superpose_params(s, c, u, phase);
-    if (fr) {
-        p.phase = fr->phase;
-        p.stop = fr->stop;
-        p.it = it;
-        p.frame = fr->frame;
-        p.mask = fr->mask;
-        p.ct2pi = fr->ct2pi;
-        p.rule = fr->rule;
-    }
-    hipLaunchKernelGGL(spot_superpose_kernel, grid, dim3(kFieldsThreads), 0, s->stream, p);
+Frame own_frame(slm_spots* s, int loops) {
+    return Frame{s->a_t.p, s->w0.p, s->w.p, s->v.p, s->stats.p, s->max_loops, nullptr, loops, 0.0,
+                 s->phase.p, nullptr, nullptr, 0.0, 0};
+}
+
+// Each launch fills its parameter block once, in the order of the struct's fields.
+// launch_tables: the four tables of the current list, whose ys, xs, zs [B][M] are on the device
+int launch_tables(slm_spots* s, const double* ys, const double* xs, const double* zs) {
+    const SeqTableParams p{ys, xs, zs, s->py.p, s->pyt.p, s->px.p, s->pxt.p, s->H, s->W, s->M, s->Mp};
+    hipLaunchKernelGGL(spot_seq_tables_kernel, dim3(grid_for(2LL * (s->H + s->W) * s->Mp), s->B), dim3(256), 0,
+                       s->stream, p);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int launch_fields(slm_spots* s, const float2* u, const int* stop = nullptr) {
-    FieldsParams p{};
-    p.u = u;
-    p.ain = s->ain_set ? s->ain : nullptr;
-    p.px = s->px;
-    p.py = s->py;
-    p.partial = s->partial;
-    p.H = s->H;
-    p.W = s->W;
-    p.Mp = s->Mp;
-    p.col_splits = s->col_splits;
-    p.cols_per_split = s->cols_per_split;
-    p.units = s->units;
-    p.stop = stop;
+int launch_fields(slm_spots* s, const float2* u, const int* stop) {
+    const FieldsParams p{u, s->ain_set ? s->ain.p : nullptr, s->px.p, s->py.p, s->partial.p, s->H, s->W, s->Mp,
+                         s->col_splits, s->cols_per_split, s->units, stop};
     hipLaunchKernelGGL(spot_fields_kernel, dim3(s->units, s->Mp / kTile, s->B), dim3(kFieldsThreads), 0, s->stream,
                        p);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int launch_update(slm_spots* s, int it, const FrameSlices* fr = nullptr) {
-    UpdateParams p{};
-    p.partial = s->partial;
-    p.a_t = s->a_t;
-    p.w_in = it == 0 ? s->w0 : s->w;
-    p.w_out = s->w;
-    p.v = s->v;
-    p.c = s->c;
-    p.stats = s->stats;
-    p.M = s->M;
-    p.Mp = s->Mp;
-    p.units = s->units;
-    p.max_loops = s->max_loops;
-    p.it = it;
-    p.feedback = s->feedback;
-    p.inv_norm = 1.0 / ((double)s->H * s->W * s->sum_a2);
-    if (fr) {
-        p.a_t = fr->a_t;
-        p.w_in = it == 0 ? fr->w_in : fr->w;
-        p.w_out = fr->w;
-        p.v = fr->v;
-        p.stats = fr->stats;
-        p.max_loops = fr->stats_loops;
-        p.stop = fr->stop;
-        p.last_it = fr->loops - 1;
-        p.tol = fr->tol;
-    }
+int launch_update(slm_spots* s, const Frame& fr, int it) {
+    const UpdateParams p{s->partial.p, fr.a_t, it == 0 ? fr.w_in : fr.w, fr.w, fr.v, s->c.p, fr.stats,
+                         s->M, s->Mp, s->units, fr.stats_loops, it,
+                         s->feedback, 1.0 / ((double)s->H * s->W * s->sum_a2),
+                         fr.stop, fr.loops - 1, fr.tol};
     hipLaunchKernelGGL(spot_update_kernel, dim3(s->B), dim3(kUpdThreads), 0, s->stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// u = the unit field of sum_m c_m exp(i D_m). Without a stop word only the frame's last iteration
+// is handed the phase; with one every iteration is, and the kernel stores it where the word says.
+int launch_superpose(slm_spots* s, const Frame& fr, int it, const float2* c, float2* u) {
+    const dim3 grid((s->W + kWaves * kTile - 1) / (kWaves * kTile), (s->H + kTile - 1) / kTile, s->B);
+    const SuperposeParams p{s->pyt.p, s->pxt.p, c, u, fr.stop || it == fr.loops - 1 ? fr.phase : nullptr,
+                            s->H, s->W, s->M, s->Mp, fr.stop, it, fr.frame, fr.mask, fr.ct2pi, fr.rule};
+    hipLaunchKernelGGL(spot_superpose_kernel, grid, dim3(kFieldsThreads), 0, s->stream, p);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -717,16 +702,14 @@ int launch_update(slm_spots* s, int it, const FrameSlices* fr = nullptr) {
 // the start of a run without a caller's phase: angle(sum_m a_T,m exp(i (D_m + theta_m)))
 int default_start(slm_spots* s) {
     if (s->custom_phase || s->u0_valid) return 0;
-    std::vector<float2> c0((size_t)s->B * s->Mp, make_float2(0.0f, 0.0f));
-    for (int b = 0; b < s->B; ++b)
-        for (int m = 0; m < s->M; ++m) {
-            double th = (double)m * kGolden;
-            th = kTwoPi * (th - std::floor(th));
-            const double a = s->host_a_t[(size_t)b * s->M + m];
-            c0[(size_t)b * s->Mp + m] = make_float2((float)(a * std::cos(th)), (float)(a * std::sin(th)));
-        }
-    RC(up(s, s->c0, c0.data(), c0.size() * sizeof(float2)));
-    RC(launch_superpose(s, s->c0, s->u0, nullptr));
+    const std::vector<float2> c0 = pad(s->B, s->M, s->Mp, make_float2(0.0f, 0.0f), [&](size_t i) {
+        double th = (double)(i % s->M) * kGolden;
+        th = kTwoPi * (th - std::floor(th));
+        const double a = s->host_a_t[i];
+        return make_float2((float)(a * std::cos(th)), (float)(a * std::sin(th)));
+    });
+    RC(up(s, s->c0.p, c0.data(), c0.size() * sizeof(float2)));
+    RC(launch_superpose(s, Frame{}, 0, s->c0.p, s->u0.p));  // no frame: nothing but the unit field is stored
     s->u0_valid = true;
     return 0;
 }
@@ -757,6 +740,23 @@ struct Timer {
     }
 };
 
+// one frame: fr.loops iterations of fields, update and superposition; the first reads `start`,
+// the others the state the one before left
+int run_frame(slm_spots* s, const Frame& fr, const float2* start, Timer& tm) {
+    for (int it = 0; it < fr.loops; ++it) {
+        RC(tm.begin(SLM_SPOTS_KERNEL_FIELDS));
+        RC(launch_fields(s, it == 0 ? start : s->u.p, fr.stop));
+        RC(tm.end());
+        RC(tm.begin(SLM_SPOTS_KERNEL_UPDATE));
+        RC(launch_update(s, fr, it));
+        RC(tm.end());
+        RC(tm.begin(SLM_SPOTS_KERNEL_SUPERPOSE));
+        RC(launch_superpose(s, fr, it, s->c.p, s->u.p));
+        RC(tm.end());
+    }
+    return 0;
+}
+
 int run_loops(slm_spots* s, int loops, double* us_per_class) {
     if (!s) return fail(SLM_ERR_ARG, "null spots handle");
     if (!s->M) return fail(SLM_ERR_STATE, "slm_spots_run before slm_spots_set_traps");
@@ -767,17 +767,7 @@ int run_loops(slm_spots* s, int loops, double* us_per_class) {
     s->seq_resumable = false;  // the run overwrites the unit field a sequence left
     RC(default_start(s));
     Timer tm{{}, {}, s->stream, us_per_class != nullptr};
-    for (int it = 0; it < loops; ++it) {
-        RC(tm.begin(SLM_SPOTS_KERNEL_FIELDS));
-        RC(launch_fields(s, it == 0 ? s->u0 : s->u));
-        RC(tm.end());
-        RC(tm.begin(SLM_SPOTS_KERNEL_UPDATE));
-        RC(launch_update(s, it));
-        RC(tm.end());
-        RC(tm.begin(SLM_SPOTS_KERNEL_SUPERPOSE));
-        RC(launch_superpose(s, s->c, s->u, it == loops - 1 ? s->phase : nullptr));
-        RC(tm.end());
-    }
+    RC(run_frame(s, own_frame(s, loops), s->u0.p, tm));
     s->has_run = true;
     s->last_loops = loops;
     if (us_per_class) {
@@ -811,21 +801,29 @@ int set_list_size(slm_spots* s, int n_traps) {
     s->has_run = false;
     s->u0_valid = false;
     plan_fields(s);
-    const size_t need = (size_t)s->B * s->units * s->Mp * sizeof(double2);
-    if (need > s->partial_cap) {
-        dev_free(s->partial);
-        s->partial_cap = 0;
-        RC(slm::dev_alloc(&s->partial, need));
-        s->partial_cap = need;
-    }
-    return 0;
+    return s->partial.need((size_t)s->B * s->units * s->Mp * sizeof(double2), s->stream);
 }
 
-int launch_table(slm_spots* s, const double* pos, const double* z, float2* out, int n, int transposed) {
-    TableParams p{pos, z, out, n, s->M, s->Mp, transposed};
-    hipLaunchKernelGGL(spot_table_kernel, dim3(grid_for((long long)n * s->Mp), s->B), dim3(256), 0, s->stream, p);
-    HIP_TRY(hipGetLastError());
-    return 0;
+// every buffer whose size the handle's shape fixes
+int size_buffers(slm_spots* s) {
+    const size_t holo = (size_t)s->H * s->W, bm = (size_t)s->B * padded_traps(s->max_traps);
+    const hipStream_t st = s->stream;
+    if (s->has_ain) RC(s->ain.need(holo * sizeof(float), st));
+    RC(s->u0.need(s->B * holo * sizeof(float2), st));
+    RC(s->u.need(s->B * holo * sizeof(float2), st));
+    RC(s->phase.need(s->B * holo * sizeof(float), st));
+    RC(s->py.need(bm * s->H * sizeof(float2), st));
+    RC(s->pyt.need(bm * s->H * sizeof(float2), st));
+    RC(s->px.need(bm * s->W * sizeof(float2), st));
+    RC(s->pxt.need(bm * s->W * sizeof(float2), st));
+    RC(s->coords.need(3 * (size_t)s->B * s->max_traps * sizeof(double), st));
+    RC(s->a_t.need(bm * sizeof(double), st));
+    RC(s->w0.need(bm * sizeof(double), st));
+    RC(s->w.need(bm * sizeof(double), st));
+    RC(s->v.need(bm * sizeof(double2), st));
+    RC(s->c.need(bm * sizeof(float2), st));
+    RC(s->c0.need(bm * sizeof(float2), st));
+    return s->stats.need((size_t)s->B * s->max_loops * 4 * sizeof(double), st);
 }
 
 }  // namespace
@@ -849,26 +847,9 @@ int slm_spots_create(int batch, int height, int width, int max_traps, int has_ai
     s->has_ain = has_ain != 0;
     s->max_loops = max_loops;
     s->sum_a2 = (double)height * width;
-    const size_t holo = (size_t)height * width, mp = padded_traps(max_traps), bm = (size_t)batch * mp;
-    int rc = 0;
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess)
-        rc = fail(SLM_ERR_HIP, "hipStreamCreate failed");
-    if (!rc && s->has_ain) rc = slm::dev_alloc(&s->ain, holo * sizeof(float));
-    if (!rc) rc = slm::dev_alloc(&s->u0, batch * holo * sizeof(float2));
-    if (!rc) rc = slm::dev_alloc(&s->u, batch * holo * sizeof(float2));
-    if (!rc) rc = slm::dev_alloc(&s->phase, batch * holo * sizeof(float));
-    if (!rc) rc = slm::dev_alloc(&s->py, bm * height * sizeof(float2));
-    if (!rc) rc = slm::dev_alloc(&s->pyt, bm * height * sizeof(float2));
-    if (!rc) rc = slm::dev_alloc(&s->px, bm * width * sizeof(float2));
-    if (!rc) rc = slm::dev_alloc(&s->pxt, bm * width * sizeof(float2));
-    if (!rc) rc = slm::dev_alloc(&s->coords, 3 * (size_t)batch * max_traps * sizeof(double));
-    if (!rc) rc = slm::dev_alloc(&s->a_t, bm * sizeof(double));
-    if (!rc) rc = slm::dev_alloc(&s->w0, bm * sizeof(double));
-    if (!rc) rc = slm::dev_alloc(&s->w, bm * sizeof(double));
-    if (!rc) rc = slm::dev_alloc(&s->v, bm * sizeof(double2));
-    if (!rc) rc = slm::dev_alloc(&s->c, bm * sizeof(float2));
-    if (!rc) rc = slm::dev_alloc(&s->c0, bm * sizeof(float2));
-    if (!rc) rc = slm::dev_alloc(&s->stats, (size_t)batch * max_loops * 4 * sizeof(double));
+    const int rc = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess
+                       ? fail(SLM_ERR_HIP, "hipStreamCreate failed")
+                       : size_buffers(s);
     if (rc) {
         spots_free(s);
         return rc;
@@ -891,34 +872,19 @@ int slm_spots_set_traps(slm_spots* s, int n_traps, const double* ys, const doubl
     if (n_traps < 1 || n_traps > s->max_traps)
         return fail(SLM_ERR_ARG, "%d traps outside 1 .. max_traps %d", n_traps, s->max_traps);
     const size_t n = (size_t)s->B * n_traps;
-    for (size_t i = 0; i < n; ++i) {
-        if (!std::isfinite(ys[i]) || !std::isfinite(xs[i]) || (zs && !std::isfinite(zs[i])))
-            return fail(SLM_ERR_ARG, "trap %zu has a non-finite coordinate", i);
-        if (intensity && !(intensity[i] > 0.0f && std::isfinite(intensity[i])))
-            return fail(SLM_ERR_ARG, "trap %zu: the intensity must be positive and finite", i);
-    }
+    RC(check_traps(n, ys, xs, zs, intensity));
     RC(slm::ensure_device());
     s->seq_resumable = false;
     RC(set_list_size(s, n_traps));
-    std::vector<double> z0(n, 0.0);
-    double *dy = s->coords, *dx = dy + n, *dz = dx + n;
-    RC(up(s, dy, ys, n * sizeof(double)));
-    RC(up(s, dx, xs, n * sizeof(double)));
-    RC(up(s, dz, zs ? zs : z0.data(), n * sizeof(double)));
-    s->host_a_t.assign(n, 1.0);
-    std::vector<double> a_t((size_t)s->B * s->Mp, 1.0), ones((size_t)s->B * s->Mp, 1.0);
-    for (int b = 0; b < s->B; ++b)
-        for (int m = 0; m < n_traps; ++m) {
-            const double a = intensity ? std::sqrt((double)intensity[(size_t)b * n_traps + m]) : 1.0;
-            s->host_a_t[(size_t)b * n_traps + m] = a;
-            a_t[(size_t)b * s->Mp + m] = a;
-        }
-    RC(up(s, s->a_t, a_t.data(), a_t.size() * sizeof(double)));
-    RC(up(s, s->w0, ones.data(), ones.size() * sizeof(double)));
-    RC(launch_table(s, dy, dz, s->py, s->H, 0));
-    RC(launch_table(s, dy, dz, s->pyt, s->H, 1));
-    RC(launch_table(s, dx, dz, s->px, s->W, 0));
-    RC(launch_table(s, dx, dz, s->pxt, s->W, 1));
+    double* d = s->coords.p;
+    RC(upload_coords(s, d, n, ys, xs, zs));
+    const std::vector<double> a_t = pad(s->B, n_traps, s->Mp, 1.0, [&](size_t i) {
+        return intensity ? std::sqrt((double)intensity[i]) : 1.0;
+    });
+    refill_host_a_t(s, a_t.data());
+    RC(up(s, s->a_t.p, a_t.data(), a_t.size() * sizeof(double)));
+    RC(upload_weights(s, s->w0.p, nullptr));
+    RC(launch_tables(s, d, d + n, d + 2 * n));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }
@@ -935,7 +901,7 @@ int slm_spots_set_ain(slm_spots* s, const float* ain) {
     if (!(sum > 0.0)) return fail(SLM_ERR_ARG, "a_in is zero everywhere");
     RC(slm::ensure_device());
     s->seq_resumable = false;
-    RC(up(s, s->ain, ain, holo * sizeof(float)));
+    RC(up(s, s->ain.p, ain, holo * sizeof(float)));
     s->sum_a2 = sum;
     s->ain_set = true;
     return 0;
@@ -950,8 +916,8 @@ int slm_spots_set_phase(slm_spots* s, const float* phase) {
     if (!phase) return 0;
     const long long n = (long long)s->B * s->H * s->W;
     // the float32 phase passes through the state buffer on its way to the start field
-    RC(up(s, s->phase, phase, n * sizeof(float)));
-    hipLaunchKernelGGL(spot_phase_kernel, dim3(grid_for(n)), dim3(256), 0, s->stream, s->phase, s->u0, n);
+    RC(up(s, s->phase.p, phase, n * sizeof(float)));
+    hipLaunchKernelGGL(spot_phase_kernel, dim3(grid_for(n)), dim3(256), 0, s->stream, s->phase.p, s->u0.p, n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->has_run = false;
@@ -962,17 +928,9 @@ int slm_spots_set_weights(slm_spots* s, const float* weights) {
     if (!s) return fail(SLM_ERR_ARG, "null spots handle");
     if (!s->M) return fail(SLM_ERR_STATE, "slm_spots_set_weights before slm_spots_set_traps");
     s->seq_resumable = false;
-    std::vector<double> w((size_t)s->B * s->Mp, 1.0);
-    if (weights)
-        for (int b = 0; b < s->B; ++b)
-            for (int m = 0; m < s->M; ++m) {
-                const float v = weights[(size_t)b * s->M + m];
-                if (!(v > 0.0f && std::isfinite(v)))
-                    return fail(SLM_ERR_ARG, "weight %d of hologram %d is not positive and finite", m, b);
-                w[(size_t)b * s->Mp + m] = v;
-            }
+    RC(check_weights(s, s->M, weights));
     RC(slm::ensure_device());
-    return up(s, s->w0, w.data(), w.size() * sizeof(double));
+    return upload_weights(s, s->w0.p, weights);
 }
 
 int slm_spots_set_feedback(slm_spots* s, float feedback) {
@@ -996,30 +954,16 @@ int slm_spots_read(slm_spots* s, float* phase, double* fields, double* stats, fl
     if (!s->has_run) return fail(SLM_ERR_STATE, "slm_spots_read before a run");
     RC(slm::ensure_device());
     HIP_TRY(hipStreamSynchronize(s->stream));
-    if (phase) RC(down(s, phase, s->phase, (size_t)s->B * s->H * s->W * sizeof(float)));
-    const size_t bm = (size_t)s->B * s->Mp;
-    if (fields) {
-        std::vector<double2> v(bm);
-        RC(down(s, v.data(), s->v, bm * sizeof(double2)));
-        for (int b = 0; b < s->B; ++b)
-            for (int m = 0; m < s->M; ++m) {
-                fields[2 * ((size_t)b * s->M + m)] = v[(size_t)b * s->Mp + m].x;
-                fields[2 * ((size_t)b * s->M + m) + 1] = v[(size_t)b * s->Mp + m].y;
-            }
-    }
+    if (phase) RC(down(s, phase, s->phase.p, (size_t)s->B * s->H * s->W * sizeof(float)));
+    if (fields) RC(read_fields(s, s->v.p, s->B, s->M, s->Mp, fields));
     if (stats) {
         std::vector<double> st((size_t)s->B * s->max_loops * 4);
-        RC(down(s, st.data(), s->stats, st.size() * sizeof(double)));
+        RC(down(s, st.data(), s->stats.p, st.size() * sizeof(double)));
         for (int b = 0; b < s->B; ++b)
             std::copy_n(&st[(size_t)b * s->max_loops * 4], (size_t)s->last_loops * 4,
                         &stats[(size_t)b * s->last_loops * 4]);
     }
-    if (weights) {
-        std::vector<double> w(bm);
-        RC(down(s, w.data(), s->w, bm * sizeof(double)));
-        for (int b = 0; b < s->B; ++b)
-            for (int m = 0; m < s->M; ++m) weights[(size_t)b * s->M + m] = (float)w[(size_t)b * s->Mp + m];
-    }
+    if (weights) RC(read_weights(s, s->w.p, s->B, s->M, s->Mp, weights));
     return 0;
 }
 
@@ -1039,16 +983,8 @@ int slm_spots_sequence(slm_spots* s, int n_frames, int n_traps, const double* ys
         return fail(SLM_ERR_ARG, "ct2pi must be finite and positive, got %g", ct2pi);
     if (resume && weights0) return fail(SLM_ERR_ARG, "a resumed sequence takes its weights from the previous one");
     const size_t bm_in = (size_t)s->B * n_traps, n = (size_t)n_frames * bm_in;
-    for (size_t i = 0; i < n; ++i) {
-        if (!std::isfinite(ys[i]) || !std::isfinite(xs[i]) || (zs && !std::isfinite(zs[i])))
-            return fail(SLM_ERR_ARG, "trap %zu has a non-finite coordinate", i);
-        if (intensity && !(intensity[i] > 0.0f && std::isfinite(intensity[i])))
-            return fail(SLM_ERR_ARG, "trap %zu: the intensity must be positive and finite", i);
-    }
-    if (weights0)
-        for (size_t i = 0; i < bm_in; ++i)
-            if (!(weights0[i] > 0.0f && std::isfinite(weights0[i])))
-                return fail(SLM_ERR_ARG, "weight %zu is not positive and finite", i);
+    RC(check_traps(n, ys, xs, zs, intensity));
+    RC(check_weights(s, n_traps, weights0));
     if (s->has_ain && !s->ain_set) return fail(SLM_ERR_STATE, "slm_spots_sequence before slm_spots_set_ain");
     if (resume && !(s->seq_resumable && s->seq_traps == n_traps))
         return fail(SLM_ERR_STATE, "resume needs a previous sequence of %d traps with no set_* or run since", n_traps);
@@ -1072,80 +1008,47 @@ int slm_spots_sequence(slm_spots* s, int n_frames, int n_traps, const double* ys
     RC(set_list_size(s, n_traps));
 
     // ---- everything the chain reads goes up once ----
-    double *dy = s->seq_coords.p, *dx = dy + n, *dz = dx + n;
-    RC(up(s, dy, ys, n * sizeof(double)));
-    RC(up(s, dx, xs, n * sizeof(double)));
-    if (zs)
-        RC(up(s, dz, zs, n * sizeof(double)));
-    else
-        HIP_TRY(hipMemsetAsync(dz, 0, n * sizeof(double), s->stream));
-    std::vector<double> a_t(F * bmp, 1.0);
-    if (intensity)
-        for (size_t fb = 0; fb < F * s->B; ++fb)
-            for (int m = 0; m < n_traps; ++m) a_t[fb * mp + m] = std::sqrt((double)intensity[fb * n_traps + m]);
+    const double *dy = s->seq_coords.p, *dx = dy + n, *dz = dx + n;
+    RC(upload_coords(s, s->seq_coords.p, n, ys, xs, zs));
+    const std::vector<double> a_t = pad(F * s->B, n_traps, mp, 1.0, [&](size_t i) {
+        return intensity ? std::sqrt((double)intensity[i]) : 1.0;
+    });
     RC(up(s, s->seq_a_t.p, a_t.data(), a_t.size() * sizeof(double)));
-    if (resume) {
+    if (resume)
         HIP_TRY(hipMemcpyAsync(s->seq_w.p, s->seq_w_last.p, bmp * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
-    } else {
-        std::vector<double> w(bmp, 1.0);
-        if (weights0)
-            for (int b = 0; b < s->B; ++b)
-                for (int m = 0; m < n_traps; ++m) w[(size_t)b * mp + m] = weights0[(size_t)b * n_traps + m];
-        RC(up(s, s->seq_w.p, w.data(), w.size() * sizeof(double)));
-    }
+    else
+        RC(upload_weights(s, s->seq_w.p, weights0));
     if (want_frames && mask) RC(up(s, s->seq_mask.p, mask, holo * sizeof(double)));
     // the handle's own list becomes the last frame's, its weights ones (the chain reads neither)
-    std::vector<double> ones(bmp, 1.0);
-    RC(up(s, s->a_t, a_t.data() + (F - 1) * bmp, bmp * sizeof(double)));
-    RC(up(s, s->w0, ones.data(), ones.size() * sizeof(double)));
+    RC(up(s, s->a_t.p, a_t.data() + (F - 1) * bmp, bmp * sizeof(double)));
+    RC(upload_weights(s, s->w0.p, nullptr));
     // the stop words start at 0 and the statistics rows a frame does not reach stay 0
     HIP_TRY(hipMemsetAsync(s->seq_iters.p, 0, F * s->B * sizeof(int), s->stream));
     HIP_TRY(hipMemsetAsync(s->seq_stats.p, 0, F * s->B * stats_loops * 4 * sizeof(double), s->stream));
 
     // ---- the chain: per frame one table launch, then its iterations ----
-    auto host_a_t = [&](size_t f) {
-        s->host_a_t.assign(bm_in, 1.0);
-        for (int b = 0; b < s->B; ++b)
-            for (int m = 0; m < n_traps; ++m)
-                s->host_a_t[(size_t)b * n_traps + m] = a_t[(f * s->B + b) * mp + m];
-    };
+    Timer untimed{{}, {}, s->stream, false};
     for (size_t f = 0; f < F; ++f) {
-        SeqTableParams tp{dy + f * bm_in, dx + f * bm_in, dz + f * bm_in, s->py, s->pyt, s->px, s->pxt, s->H, s->W,
-                          n_traps, mp};
-        hipLaunchKernelGGL(spot_seq_tables_kernel, dim3(grid_for(2LL * (s->H + s->W) * mp), s->B), dim3(256), 0,
-                           s->stream, tp);
-        HIP_TRY(hipGetLastError());
+        RC(launch_tables(s, dy + f * bm_in, dx + f * bm_in, dz + f * bm_in));
         const bool first = f == 0 && !resume;
         if (first) {
-            host_a_t(0);
+            refill_host_a_t(s, a_t.data());
             RC(default_start(s));
         }
-        FrameSlices fr{};
-        fr.a_t = s->seq_a_t.p + f * bmp;
-        fr.w_in = s->seq_w.p + f * bmp;
-        fr.w = s->seq_w.p + (f + 1) * bmp;
-        fr.v = s->seq_v.p + f * bmp;
-        fr.stats = s->seq_stats.p + f * s->B * stats_loops * 4;
-        fr.stats_loops = stats_loops;
-        fr.stop = s->seq_iters.p + f * s->B;
-        fr.loops = first ? loops_first : loops;
-        fr.tol = tol;
-        fr.phase = want_phases ? s->seq_phase.p + f * s->B * holo : nullptr;
-        fr.frame = want_frames ? s->seq_out.p + f * s->B * holo : nullptr;
-        fr.mask = want_frames && mask ? s->seq_mask.p : nullptr;
-        fr.ct2pi = ct2pi;
-        fr.rule = rule;
-        for (int it = 0; it < fr.loops; ++it) {
-            RC(launch_fields(s, first && it == 0 ? s->u0 : s->u, fr.stop));
-            RC(launch_update(s, it, &fr));
-            RC(launch_superpose(s, s->c, s->u, nullptr, &fr, it));
-        }
+        const size_t fb = f * s->B;  // slice f of every sequence buffer, in the order of Frame's fields
+        const Frame fr{s->seq_a_t.p + f * bmp, s->seq_w.p + f * bmp, s->seq_w.p + (f + 1) * bmp, s->seq_v.p + f * bmp,
+                       s->seq_stats.p + fb * stats_loops * 4, stats_loops, s->seq_iters.p + fb,
+                       first ? loops_first : loops, tol,
+                       want_phases ? s->seq_phase.p + fb * holo : nullptr,
+                       want_frames ? s->seq_out.p + fb * holo : nullptr,
+                       want_frames && mask ? s->seq_mask.p : nullptr, ct2pi, rule};
+        RC(run_frame(s, fr, first ? s->u0.p : s->u.p, untimed));
     }
     HIP_TRY(hipMemcpyAsync(s->seq_w_last.p, s->seq_w.p + F * bmp, bmp * sizeof(double), hipMemcpyDeviceToDevice,
                            s->stream));
 
     // ---- the handle is as after slm_spots_set_traps with the last list ----
-    host_a_t(F - 1);
+    refill_host_a_t(s, a_t.data() + (F - 1) * bmp);
     s->u0_valid = false;
     s->has_run = false;
     s->seq_frames = n_frames;
@@ -1169,22 +1072,9 @@ int slm_spots_sequence_read(slm_spots* s, unsigned char* frames, float* phases, 
     const size_t F = (size_t)s->seq_frames, fb = F * s->B, holo = (size_t)s->H * s->W;
     if (frames) RC(down(s, frames, s->seq_out.p, fb * holo));
     if (phases) RC(down(s, phases, s->seq_phase.p, fb * holo * sizeof(float)));
-    if (fields) {
-        std::vector<double2> v(fb * mp);
-        RC(down(s, v.data(), s->seq_v.p, v.size() * sizeof(double2)));
-        for (size_t k = 0; k < fb; ++k)
-            for (int m = 0; m < mt; ++m) {
-                fields[2 * (k * mt + m)] = v[k * mp + m].x;
-                fields[2 * (k * mt + m) + 1] = v[k * mp + m].y;
-            }
-    }
+    if (fields) RC(read_fields(s, s->seq_v.p, fb, mt, mp, fields));
     if (stats) RC(down(s, stats, s->seq_stats.p, fb * s->seq_loops * 4 * sizeof(double)));
-    if (weights) {
-        std::vector<double> w(fb * mp);
-        RC(down(s, w.data(), s->seq_w.p + (size_t)s->B * mp, w.size() * sizeof(double)));
-        for (size_t k = 0; k < fb; ++k)
-            for (int m = 0; m < mt; ++m) weights[k * mt + m] = (float)w[k * mp + m];
-    }
+    if (weights) RC(read_weights(s, s->seq_w.p + (size_t)s->B * mp, fb, mt, mp, weights));
     if (iters) RC(down(s, iters, s->seq_iters.p, fb * sizeof(int)));
     return 0;
 }
@@ -1207,8 +1097,8 @@ int slm_spots_fields(int batch, int height, int width, int n_traps, const double
     int rc = slm_spots_set_traps(s, n_traps, ys, xs, zs, nullptr);
     if (!rc && ain) rc = slm_spots_set_ain(s, ain);
     if (!rc) rc = slm_spots_set_phase(s, phase);
-    if (!rc) rc = launch_fields(s, s->u0);
-    if (!rc) rc = launch_update(s, 0);
+    if (!rc) rc = launch_fields(s, s->u0.p, nullptr);
+    if (!rc) rc = launch_update(s, own_frame(s, 1), 0);
     if (!rc) {
         s->has_run = true;
         s->last_loops = 1;
@@ -1225,14 +1115,12 @@ int slm_spots_superpose(int batch, int height, int width, int n_traps, const dou
     RC(slm_spots_create(batch, height, width, n_traps, 0, 1, &s));
     int rc = slm_spots_set_traps(s, n_traps, ys, xs, zs, nullptr);
     if (!rc) {
-        std::vector<float2> c((size_t)batch * s->Mp, make_float2(0.0f, 0.0f));
-        for (int b = 0; b < batch; ++b)
-            for (int m = 0; m < n_traps; ++m)
-                c[(size_t)b * s->Mp + m] = make_float2((float)c_re_im[2 * ((size_t)b * n_traps + m)],
-                                                       (float)c_re_im[2 * ((size_t)b * n_traps + m) + 1]);
-        rc = up(s, s->c, c.data(), c.size() * sizeof(float2));
+        const std::vector<float2> c = pad(batch, n_traps, s->Mp, make_float2(0.0f, 0.0f), [&](size_t i) {
+            return make_float2((float)c_re_im[2 * i], (float)c_re_im[2 * i + 1]);
+        });
+        rc = up(s, s->c.p, c.data(), c.size() * sizeof(float2));
     }
-    if (!rc) rc = launch_superpose(s, s->c, s->u, s->phase);
+    if (!rc) rc = launch_superpose(s, own_frame(s, 1), 0, s->c.p, s->u.p);
     if (!rc) {
         s->has_run = true;
         s->last_loops = 1;

@@ -1,7 +1,8 @@
 """Trap trajectories (slm_spots_sequence) on the MI355X: the identities that
 must hold bit for bit (frames of one list are one long run, a sequence cut in
-two with resume is the uncut one, a frame the device stopped is that frame run
-for exactly as many iterations), parity of a moving list with the float64
+two with resume is the uncut one, a handle whose buffers have grown computes
+what a fresh one does, a frame the device stopped is that frame run for
+exactly as many iterations), parity of a moving list with the float64
 NumPy chain (tests/spots_sequence_reference.py) from a warm start as
 tests/test_gpu_spots.py sets it up, the tolerance stop against the reference's
 iteration counts, and the refusals."""
@@ -104,6 +105,39 @@ def test_resume_is_the_uncut_sequence(gpu):
     for a, hd, tl in zip(whole, head, tail):
         np.testing.assert_array_equal(a, np.concatenate([hd, tl]))
     assert not np.array_equal(whole[1][2], whole[1][3])
+
+
+# ---------------------------------------------------------------------------
+# 2b. a handle whose buffers have grown computes what a fresh one does
+# ---------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_a_handle_that_has_grown(gpu):
+    """One handle takes a short sequence of few traps, a longer one of more
+    traps with a mask (every sequence buffer and the partial sums grow), a
+    list of max_traps traps and a run (the partial sums grow again), and the
+    first sequence once more in buffers that are now larger than it needs.
+    Everything read back after each call equals the same call on a fresh handle."""
+    h, w, max_traps, max_loops = 45, 70, 70, 6
+    mask = _mask((h, w))
+
+    def sequence(m, n_frames, mk):
+        def call(sp):
+            sp.sequence(*_cols([ssr.trajectory(h, w, m, 4, n_frames)]), loops_first=6, loops=3, tol=0.0, mask=mk,
+                        ct2pi=200, frames=True, phases=True)
+            return sp.sequence_read(phases=True)
+        return call
+
+    def run(sp):
+        sp.set_traps(*sr.trap_list(h, w, max_traps, 4))
+        sp.run(max_loops)
+        return sp.read()
+
+    with gpu.Spots(1, h, w, max_traps, False, max_loops) as grown:
+        for call in (sequence(5, 2, None), sequence(33, 5, mask), run, sequence(5, 2, None)):
+            got = call(grown)
+            with gpu.Spots(1, h, w, max_traps, False, max_loops) as fresh:
+                _assert_same(got, call(fresh))
+    assert got[0].shape == (2, 1, h, w) and len(np.unique(got[0])) > 100  # real frames, not a constant
 
 
 # ---------------------------------------------------------------------------
