@@ -28,10 +28,24 @@
 // 60-112): complex128 state, float64 statistics (E = |C|^2 unrounded),
 // amplitudes as numpy forms them (sqrt(uint8) -> float16, sqrt(float32) ->
 // float32), the cold start's ifft2 of a float amplitude rounded to complex64.
+//
+// This file, top to bottom:
+//  1. the element-wise, statistics and transpose kernels;
+//  2. what the back ends share on the host: launch helpers, table uploads,
+//     mixed-radix line plans, and AnySizeEngine -- every Engine method but
+//     enqueue, written once on two device primitives a back end provides (the
+//     unscaled 2-D transform at its precision, the GD field as complex64);
+//  3. LinesEngine: the line transforms (chirp-z plans, its GS / GD loops);
+//  4. TiledEngine: mixed radix and radix plans, one launch structure and one
+//     set of buffers; they differ in how a tile is launched (row, col) and in
+//     their tables, nowhere else;
+//  5. the choice (generic_choose: back end, precision, tiles -- every
+//     environment knob and occupancy query of this file) and generic_create.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 #include "../../include/slm_hip.h"
@@ -41,59 +55,6 @@
 #include "radix_c128.hpp"
 
 namespace slm {
-
-struct GenericEngine : Engine {
-    ~GenericEngine() override;
-    void* target_stage(const PlanState& v) override { return v.tgt; }  // kept row-major as uploaded
-    int land_target(PlanState&, const void*) override { return 0; }
-    int land_field(PlanState& v, const float* field) override;
-    int enqueue(PlanState& v, int loops, double tol, int checked, float wa, bool phase_set, bool field_set) override;
-    int set_precision(PlanState&, int) override { return fail(SLM_ERR_STATE, "any-size engines are rebuilt"); }
-    int read_field(PlanState& v, bool fresh, float* field) override;
-    int fft2(PlanState& v, const float* in, float* out, int inverse) override;
-    int fft2_z(PlanState& v, const double2* in, double2* out, int inverse) override;
-    int intensity(PlanState& v) override;
-    long long kernel_bytes(const PlanState& v, int cls) const override;
-    int kind() const { return rz ? (prec == PREC_F32 ? 5 : 4) : mr ? 3 : 2; }  // 2: line transforms
-    void codes(const PlanState&, int* col_engine, int* row_engine) const override { *col_engine = *row_engine = kind(); }
-    void layout(int* x_log2, int* y_log2) const override { *x_log2 = *y_log2 = 0; }  // row-major
-    void info(const PlanState& v, int info[8]) const override {
-        const int i[8] = {0, v.nwg, 0, 0, 1, -1, -1, v.prec};  // no fused-engine tiles or plan keys
-        std::copy(i, i + 8, info);
-    }
-    int generic_info(int info[8]) const override;
-    // device complex64 [B][H][W] transforms and the GD field (in may equal out)
-    int fft2_c64(const PlanState& v, const float2* in, float2* out, int inverse);
-    int field_c64(const PlanState& v, float2* out);
-
-    // mixed-radix back end: line plans (twiddles, digit reversal) of both sides
-    bool mr = false;
-    // complex128 radix-plan back end (mr is set too: same launch structure and
-    // buffers; its line plans hold Stockham twiddle tables and the identity order)
-    bool rz = false;
-    int rkey = -1, ckey = -1;  // plan keys (plans.hpp) of the row / column transforms
-    int rz_cw = 0;             // columns per column tile
-    int rz_lay = 0;            // state layout between the passes (radix_c128.hpp LAY_RM / LAY_B2)
-    int prec = PREC_F64;       // PREC_F32: complex64 radix kernels (the state buffers then hold float2)
-    float* tgt_blk = nullptr;  // the target as float in the radix kernels' B2 layout (rebuilt per run)
-    bool big = false;        // a radix outside mr::small_radix in either plan (7, 11, 13)
-    mr::LinePlan pw, ph;     // row (length W) and column (length H) transforms
-    int rpw = 1;             // rows per row tile
-    int cw_log2 = 0;         // columns per column tile = 2^cw_log2
-    int nwg_col = 0;         // column tiles per hologram
-    std::vector<void*> tables;  // device twiddle / reversal tables
-    float* ain_rev = nullptr;   // a_in with rows in the row transform's digit-reversed order (has_ain)
-    // line-transform back end: the row (length W) and column (length H) transforms
-    mr::LineArgs lw, lh;
-    bool big_w = false, big_h = false;  // their plans need the odd-radix kernels
-    // state (row-major complex128 [B][H][W])
-    double2* a = nullptr;    // lines GS: A; GD: the inverse-transformed gradient g. Mixed radix: row-pass output
-    double2* b = nullptr;    // lines GS: B, then C in place; GD: u, then F in place. Mixed radix: column-pass output
-    double2* d = nullptr;    // lines GS: D; GD: G
-    double2* x = nullptr;    // GD: the field x
-    double2* tmp = nullptr;  // lines: the row-transformed image
-    double2* tmp2 = nullptr; // lines: the transposed image [B][W][H]
-};
 
 namespace {
 
@@ -376,34 +337,18 @@ __global__ void __launch_bounds__(256) k_transpose(const double2* in, double2* o
     }
 }
 
-// 1-D transforms of `lines` rows of the line plan's length
-int line_pass(const GenericEngine* g, const mr::LineArgs& base, bool big, const double2* in, double2* out,
-              long long lines, bool inverse, hipStream_t st) {
-    if (lines > 0x7fffffffLL) return fail(SLM_ERR_UNSUPPORTED, "line transforms: too many lines");
-    mr::LineArgs a = base;
-    a.in = in;
-    a.out = out;
-    a.inverse = inverse ? 1 : 0;
-    if (mr::mr_line_launch(big, a, (int)lines, (size_t)a.pl.n * sizeof(double2), st))
-        return fail(SLM_ERR_HIP, "line transform launch failed");
-    return 0;
+// ------------------------------------------------------------------------
+// 2. shared by the back ends (host side)
+// ------------------------------------------------------------------------
+// an element-wise kernel over n elements (every one takes n as its last parameter)
+template <typename K, typename... A>
+void each(K k, hipStream_t st, long long n, A... args) {
+    hipLaunchKernelGGL(k, dim3(grid_of(n)), dim3(kGT), 0, st, args..., n);
 }
 
-// out = op(in): forward or inverse (unscaled) 2-D transform of [B][H][W]
-// complex128 as rows -> transpose -> rows -> transpose; in may equal out
-int dft2(GenericEngine* g, const PlanState& v, const double2* in, double2* out, bool inverse) {
-    hipStream_t st = v.stream;
-    if (int rc = line_pass(g, g->lw, g->big_w, in, g->tmp, (long long)v.B * v.H, inverse, st)) return rc;
-    hipLaunchKernelGGL(k_transpose, dim3((v.W + 31) / 32, (v.H + 31) / 32, v.B), dim3(256), 0, st, g->tmp, g->tmp2,
-                       v.H, v.W);
-    if (int rc = line_pass(g, g->lh, g->big_h, g->tmp2, g->tmp2, (long long)v.B * v.W, inverse, st)) return rc;
-    hipLaunchKernelGGL(k_transpose, dim3((v.H + 31) / 32, (v.W + 31) / 32, v.B), dim3(256), 0, st, g->tmp2, out,
-                       v.W, v.H);
-    G_HIP(hipGetLastError());
-    return 0;
-}
-
-StatsParams stats_of(const PlanState& v, double tol, int iter) {
+// one (hologram, iteration) slab -> stats; tol < 0: no stop flags (k_reduce_iter
+// sets them for checked runs only)
+void reduce_iter(const PlanState& v, double tol, int iter) {
     StatsParams s{};
     s.partials = v.partials;
     s.stats = v.stats;
@@ -415,12 +360,39 @@ StatsParams stats_of(const PlanState& v, double tol, int iter) {
     s.max_loops = v.max_loops;
     s.nwg = v.nwg;
     s.iter = iter;
-    return s;
+    hipLaunchKernelGGL(k_reduce_iter, dim3(v.B), dim3(256), 0, v.stream, s);
 }
 
-// ------------------------------------------------------------------------
-// mixed-radix back end (host side)
-// ------------------------------------------------------------------------
+// a timed run's event pair around a launch (slm_plan_run_timed; the any-size
+// engine launches directly, so the events are recorded on the plan stream)
+struct Mark {
+    const PlanState& v;
+    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
+    Mark(const PlanState& vv, int cls) : v(vv) {
+        if (v.timing && !v.timing->next(cls, &ev)) (void)hipEventRecord(ev->first, v.stream);
+    }
+    ~Mark() {
+        if (ev) (void)hipEventRecord(ev->second, v.stream);
+    }
+};
+
+// Device tables of one line plan: twiddles and output order, and for a chirp-z
+// line the chirp and the transform of its kernel. They upload in pairs: both
+// allocations, then both copies (the order of the hipMalloc calls is kept, see
+// the build() of each engine).
+struct LineTables {
+    DevBuf<void> tw, rev, chirp, bhat;
+};
+int upload_pair(DevBuf<void>& a, const void* host_a, size_t bytes_a, DevBuf<void>& b, const void* host_b,
+                size_t bytes_b, hipStream_t st) {
+    RC(a.need(bytes_a, st));
+    RC(b.need(bytes_b, st));
+    G_HIP(hipMemcpyAsync(a.p, host_a, bytes_a, hipMemcpyHostToDevice, st));
+    G_HIP(hipMemcpyAsync(b.p, host_b, bytes_b, hipMemcpyHostToDevice, st));
+    G_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 // DIF stage radices of a length: 8s (then a 4 or a 2) for the powers of two,
 // then 3, 5, 7, 11, 13; false if another prime divides n or n is too long
 bool mr_radices(int n, std::vector<int>& rad) {
@@ -451,86 +423,18 @@ bool mr_radices(int n, std::vector<int>& rad) {
     return t == 1 && (int)rad.size() <= mr::kMaxPass;
 }
 
-// $SLM_GENERIC_ENGINE=bluestein (alias: gemm, r05's name of that back end)
-// sends every side through the line transforms, chirp-z included
-bool mr_forced_lines() {
-    const char* e = std::getenv("SLM_GENERIC_ENGINE");
-    return e && (!std::strcmp(e, "bluestein") || !std::strcmp(e, "gemm"));
-}
-
-bool mr_shape_ok(int H, int W) {
+// the mixed-radix plan of n uses a radix outside mr::small_radix (7, 11, 13):
+// its launches take the kernels built for the full radix set
+bool big_radix(int n) {
     std::vector<int> r;
-    return !mr_forced_lines() && mr_radices(H, r) && mr_radices(W, r);
-}
-
-bool mr_big(int H, int W) {
-    std::vector<int> rh, rw;
-    if (!mr_radices(H, rh) || !mr_radices(W, rw)) return false;
-    for (const auto* v : {&rh, &rw})
-        for (int r : *v)
-            if (!mr::small_radix(r)) return true;
+    if (!mr_radices(n, r)) return false;
+    for (int x : r)
+        if (!mr::small_radix(x)) return true;
     return false;
 }
 
-// Tiles of the two launches. A launch of `wgs` workgroups of `e` elements on
-// `cus` CUs that hold `occ` of them at once takes about rounds x (workgroups
-// per CU in a round) x e: so the rows per row tile / columns per column tile
-// minimise ceil(wgs / (cus occ)) * min(occ, ceil(wgs / cus)) * e (a grid one
-// workgroup too large for a round doubles the launch: 1080 rows in 540
-// two-row tiles on 512 slots did, 62.6 against ~35 us). Column tiles that tie
-// go to 2 columns (32-B row segments), then the narrower: 1080 x 1920 columns
-// in tiles of 2 measured 48.2 us against 58.0 in tiles of 1 and 55.0 in tiles
-// of 4 (profiles/r05/mr_tiles_s13.txt); row tiles that tie go to the wider.
-// $SLM_MR_RPW / $SLM_MR_CW override.
-struct MrTiling {
-    int rpw = 1, cw_log2 = 0;
-};
-MrTiling mr_tiling(int B, int H, int W) {
-    MrTiling t;
-    const bool big = mr_big(H, W);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
-    auto cost = [&](long long wgs, int occ, long long e) {
-        const long long slots = (long long)cus * occ;
-        const long long rounds = (wgs + slots - 1) / slots;
-        const long long per = std::min<long long>(occ, (wgs + cus - 1) / cus);
-        return rounds * per * e;
-    };
-    long long best = -1;
-    for (int r = 1; r == 1 || (long long)r * W <= mr::kTileElems; r *= 2) {
-        if (r > 1 && r > H) break;
-        const int occ = mr::mr_row_occupancy(mr::RO_GS, big, (size_t)r * W * sizeof(double2));
-        if (occ < 1) continue;
-        const long long c = cost((long long)B * ((H + r - 1) / r), occ, (long long)r * W);
-        if (best < 0 || c <= best) {
-            best = c;
-            t.rpw = r;
-        }
-    }
-    best = -1;
-    for (int c : {1, 0, 2, 3, 4}) {  // tie order
-        if (c > 0 && (((long long)H << c) > mr::kTileElems || (1 << c) > 2 * W)) continue;
-        const int occ = mr::mr_col_occupancy(mr::CO_GS, big, ((size_t)H << c) * sizeof(double2));
-        if (occ < 1) continue;
-        const long long v = cost((long long)B * ((W + (1 << c) - 1) >> c), occ, (long long)H << c);
-        if (best < 0 || v < best) {
-            best = v;
-            t.cw_log2 = c;
-        }
-    }
-    if (const char* e = std::getenv("SLM_MR_RPW")) t.rpw = std::max(1, std::min(H, std::atoi(e)));
-    if (const char* e = std::getenv("SLM_MR_CW")) {
-        int c = 0;
-        while (c < 4 && (2 << c) <= std::atoi(e)) ++c;
-        t.cw_log2 = c;
-    }
-    return t;
-}
-
 // twiddles exp(-2 pi i t / n) and the DIF output order's natural indices
-int mr_plan_line(GenericEngine* g, int n, mr::LinePlan* pl, hipStream_t st, std::vector<int>* rev_out = nullptr) {
+int mr_plan_line(LineTables& t, int n, mr::LinePlan* pl, hipStream_t st, std::vector<int>* rev_out = nullptr) {
     std::vector<int> rad;
     if (!mr_radices(n, rad)) return fail(SLM_ERR_UNSUPPORTED, "mixed radix: unsupported length");
     pl->n = n;
@@ -554,42 +458,145 @@ int mr_plan_line(GenericEngine* g, int n, mr::LinePlan* pl, hipStream_t st, std:
         }
         rev[e] = k;
     }
-    void *dtw = nullptr, *drev = nullptr;
-    if (hipMalloc(&dtw, tw.size() * sizeof(double)) != hipSuccess) return fail(SLM_ERR_HIP, "mixed radix: allocation");
-    g->tables.push_back(dtw);
-    if (hipMalloc(&drev, rev.size() * sizeof(int)) != hipSuccess) return fail(SLM_ERR_HIP, "mixed radix: allocation");
-    g->tables.push_back(drev);
-    G_HIP(hipMemcpyAsync(dtw, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    G_HIP(hipMemcpyAsync(drev, rev.data(), rev.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    G_HIP(hipStreamSynchronize(st));
-    pl->tw = static_cast<const double2*>(dtw);
-    pl->rev = static_cast<const int*>(drev);
+    RC(upload_pair(t.tw, tw.data(), tw.size() * sizeof(double), t.rev, rev.data(), rev.size() * sizeof(int), st));
+    pl->tw = static_cast<const double2*>(t.tw.p);
+    pl->rev = static_cast<const int*>(t.rev.p);
     if (rev_out) *rev_out = rev;
     return 0;
 }
 
-bool plan_big(int n) {
-    std::vector<int> r;
-    if (!mr_radices(n, r)) return false;
-    for (int x : r)
-        if (!mr::small_radix(x)) return true;
-    return false;
+int mr_roots(hipStream_t st) {
+    std::vector<double2> roots((mr::kMaxRadix + 1) * mr::kMaxRadix, make_double2(0.0, 0.0));
+    for (int R = 1; R <= mr::kMaxRadix; ++R)
+        for (int q = 0; q < R; ++q) {
+            const double ang = 2.0 * M_PI * (double)q / (double)R;
+            roots[R * mr::kMaxRadix + q] = make_double2(std::cos(ang), -std::sin(ang));
+        }
+    if (mr::mr_set_roots(roots.data(), st)) return fail(SLM_ERR_HIP, "mixed radix: root table upload failed");
+    return 0;
 }
 
+// What every back end is to a plan. A back end allocates in build(), runs the
+// iterations in enqueue() and provides the two device primitives; the rest of
+// the Engine interface is written here, once, on top of them.
+struct AnySizeEngine : Engine {
+    const AnySizeChoice ch;
+    // state every back end has (row-major complex128 [B][H][W]; the complex64
+    // radix kernels keep float2 in the same buffers). Lines GS: A, then B and C
+    // in place; GD: the inverse-transformed gradient g, then u and F in place.
+    // Tiled: row-pass output, column-pass output. x: the GD field.
+    DevBuf<double2> a, b, x;
+
+    explicit AnySizeEngine(const AnySizeChoice& c) : ch(c) {}
+    virtual int build(const PlanState& v) = 0;
+    // out = fft2 / unscaled ifft2 of in, device [B][H][W] at ch.prec (complex64
+    // behind the pointers at PREC_F32); in may equal out
+    virtual int transform(const PlanState& v, const double2* in, double2* out, bool inverse) = 0;
+    // the GD field x, row-major complex64
+    virtual int field_c64(const PlanState& v, float2* out) = 0;
+
+    void* target_stage(const PlanState& v) override { return v.tgt; }  // kept row-major as uploaded
+    int land_target(PlanState&, const void*) override { return 0; }
+    int land_field(PlanState& v, const float* field) override {
+        HIP_TRY(hipMemcpyAsync(v.field0, field, (size_t)v.B * v.holo * sizeof(float2), hipMemcpyHostToDevice,
+                               v.stream));
+        return 0;
+    }
+    int set_precision(PlanState&, int) override { return fail(SLM_ERR_STATE, "any-size engines are rebuilt"); }
+    int read_field(PlanState& v, bool fresh, float* field) override {
+        if (!fresh) {
+            if (!x.p) return fail(SLM_ERR_STATE, "the field is the state of GD plans");
+            RC(field_c64(v, v.xa));
+        }
+        return copy_sync(field, fresh ? v.field0 : v.xa, (size_t)v.B * v.holo * sizeof(float2),
+                         hipMemcpyDeviceToHost, v.stream);
+    }
+    // device complex64 [B][H][W] (in may equal out)
+    int fft2_c64(const PlanState& v, const float2* in, float2* out, int inverse) {
+        if (ch.prec == PREC_F32)  // complex64 radix kernels: straight on the caller's buffers
+            return transform(v, reinterpret_cast<const double2*>(in), reinterpret_cast<double2*>(out), inverse != 0);
+        const long long n = (long long)v.B * v.holo;
+        each(k_c64_to_c128, v.stream, n, in, b.p);
+        RC(transform(v, b.p, b.p, inverse != 0));
+        each(k_c128_to_c64, v.stream, n, b.p, out);
+        G_HIP(hipGetLastError());
+        return 0;
+    }
+    // row-major in place through the plan's staging buffer
+    int fft2(PlanState& v, const float* in, float* out, int inverse) override {
+        const size_t bytes = (size_t)v.B * v.holo * sizeof(float2);
+        hipError_t e = hipMemcpyAsync(v.xa, in, bytes, hipMemcpyHostToDevice, v.stream);
+        if (e != hipSuccess) return fail(SLM_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
+        RC(fft2_c64(v, v.xa, v.xa, inverse));
+        return copy_sync(out, v.xa, bytes, hipMemcpyDeviceToHost, v.stream);
+    }
+    int fft2_z(PlanState& v, const double2* in, double2* out, int inverse) override {
+        if (ch.prec != PREC_F64) return fail(SLM_ERR_STATE, "fft2_c128 on a complex64 engine");
+        return transform(v, in, out, inverse != 0);
+    }
+    int intensity(PlanState& v) override {
+        const long long n = (long long)v.B * v.holo;
+        if (ch.prec == PREC_F32) {
+            float2* b32 = reinterpret_cast<float2*>(b.p);
+            each(k_phase_exp_c64, v.stream, n, v.phase_in, b32);
+            RC(transform(v, b.p, b.p, false));
+            each(k_abs2_c64, v.stream, n, b32, v.e_out);
+        } else {
+            each(k_phase_exp, v.stream, n, v.phase_in, b.p);
+            RC(transform(v, b.p, b.p, false));
+            each(k_abs2, v.stream, n, b.p, v.e_out);
+        }
+        G_HIP(hipGetLastError());
+        return 0;
+    }
+    long long kernel_bytes(const PlanState& v, int cls) const override {
+        if (ch.kind == 2) return 0;  // line transforms: no column / row kernel classes
+        // mixed radix / radix plans, complex128 state (complex64: z = 8): column pass
+        // in z + T + out z (GD statistics: in + T); row pass in z + out z (+ a_in)
+        // (+ GD field read and write 2z)
+        const long long px = (long long)v.B * v.holo;
+        const long long tb = v.tt == SLM_TGT_U8 ? 1 : 4;
+        const long long ab = v.has_ain ? 4 : 0;
+        const long long z = ch.prec == PREC_F32 ? 8 : 16;
+        switch (cls) {
+            case SLM_KERNEL_COL_MAIN: return px * (2 * z + tb);
+            case SLM_KERNEL_ROW_MAIN: return px * (2 * z + ab + (v.algo == SLM_ALGO_GD ? 2 * z : 0));
+            case SLM_KERNEL_GD_STATS: return px * (z + tb);
+            default: return 0;
+        }
+    }
+    void codes(const PlanState&, int* col_engine, int* row_engine) const override {
+        *col_engine = *row_engine = ch.kind;
+    }
+    void layout(int* x_log2, int* y_log2) const override { *x_log2 = *y_log2 = 0; }  // row-major
+    void info(const PlanState& v, int info[8]) const override {
+        const int i[8] = {0, v.nwg, 0, 0, 1, -1, -1, v.prec};  // no fused-engine tiles or plan keys
+        std::copy(i, i + 8, info);
+    }
+    int generic_info(int info[8]) const override {
+        const int i[8] = {ch.kind, ch.prec, ch.rkey, ch.ckey, ch.rpw, ch.cw, ch.lay, ch.kind == 2 ? 0 : ch.nwg};
+        std::copy(i, i + 8, info);
+        return 0;
+    }
+};
+
+// ------------------------------------------------------------------------
+// 3. line transforms
+// ------------------------------------------------------------------------
 // Line transform of length n (mr::LineArgs): direct where n has a mixed-radix
 // plan (unless `chirp_z`), else Bluestein over the smallest M >= 2n - 1 made of
 // the radices 2, 3, 4, 5, 8 (the small-radix kernels): the chirp w_j =
 // exp(i pi j^2 / n) (angle from j^2 mod 2n, exact) and bhat = FFT_M(b) / M in
 // the DIF output order, b_m = w_m for m < n, b_(M - m) = w_m for 0 < m < n,
 // else 0 (one O(M^2) float64 DFT at plan creation, from a table of the M roots)
-int line_plan(GenericEngine* g, int n, bool chirp_z, mr::LineArgs* la, bool* big, hipStream_t st) {
+int line_plan(LineTables& t, int n, bool chirp_z, mr::LineArgs* la, bool* big, hipStream_t st) {
     std::vector<int> rad;
     *la = mr::LineArgs{};
     la->n = n;
     if (!chirp_z && mr_radices(n, rad)) {
         la->direct = 1;
-        *big = plan_big(n);
-        return mr_plan_line(g, n, &la->pl, st);
+        *big = big_radix(n);
+        return mr_plan_line(t, n, &la->pl, st);
     }
     int M = std::max(1, 2 * n - 1);
     auto smooth5 = [](int m) {
@@ -603,9 +610,9 @@ int line_plan(GenericEngine* g, int n, bool chirp_z, mr::LineArgs* la, bool* big
                     "unsupported side: a side over 4096 with a prime factor above 13, or any side over "
                     "8192, does not fit one workgroup's chirp-z line (8192 points)");
     std::vector<int> rev;
-    if (int rc = mr_plan_line(g, M, &la->pl, st, &rev)) return rc;
+    if (int rc = mr_plan_line(t, M, &la->pl, st, &rev)) return rc;
     la->direct = 0;
-    *big = plan_big(M);
+    *big = big_radix(M);
     std::vector<double> chirp((size_t)n * 2), b((size_t)M * 2, 0.0), bh((size_t)M * 2);
     for (long long j = 0; j < n; ++j) {
         const double ang = M_PI * (double)((j * j) % (2LL * n)) / (double)n;
@@ -644,33 +651,435 @@ int line_plan(GenericEngine* g, int n, bool chirp_z, mr::LineArgs* la, bool* big
         bh[(size_t)e * 2] = bhat[(size_t)rev[e] * 2];
         bh[(size_t)e * 2 + 1] = bhat[(size_t)rev[e] * 2 + 1];
     }
-    void *dc = nullptr, *db = nullptr;
-    if (hipMalloc(&dc, chirp.size() * sizeof(double)) != hipSuccess) return fail(SLM_ERR_HIP, "line transforms: allocation");
-    g->tables.push_back(dc);
-    if (hipMalloc(&db, bh.size() * sizeof(double)) != hipSuccess) return fail(SLM_ERR_HIP, "line transforms: allocation");
-    g->tables.push_back(db);
-    G_HIP(hipMemcpyAsync(dc, chirp.data(), chirp.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    G_HIP(hipMemcpyAsync(db, bh.data(), bh.size() * sizeof(double), hipMemcpyHostToDevice, st));
-    G_HIP(hipStreamSynchronize(st));
-    la->chirp = static_cast<const double2*>(dc);
-    la->bhat = static_cast<const double2*>(db);
+    RC(upload_pair(t.chirp, chirp.data(), chirp.size() * sizeof(double), t.bhat, bh.data(), bh.size() * sizeof(double),
+                   st));
+    la->chirp = static_cast<const double2*>(t.chirp.p);
+    la->bhat = static_cast<const double2*>(t.bhat.p);
     return 0;
 }
 
-int mr_roots(hipStream_t st) {
-    std::vector<double2> roots((mr::kMaxRadix + 1) * mr::kMaxRadix, make_double2(0.0, 0.0));
-    for (int R = 1; R <= mr::kMaxRadix; ++R)
-        for (int q = 0; q < R; ++q) {
-            const double ang = 2.0 * M_PI * (double)q / (double)R;
-            roots[R * mr::kMaxRadix + q] = make_double2(std::cos(ang), -std::sin(ang));
+struct LinesEngine : AnySizeEngine {
+    using AnySizeEngine::AnySizeEngine;
+    DevBuf<double2> d;     // GS: D; GD: G
+    DevBuf<double2> tmp;   // the row-transformed image
+    DevBuf<double2> tmp2;  // the transposed image [B][W][H]
+    mr::LineArgs lw, lh;   // the row (length W) and column (length H) transforms
+    bool big_w = false, big_h = false;  // their plans need the odd-radix kernels
+    LineTables tab_w, tab_h;
+
+    // hipMalloc order (kept as it always was: the order of two allocations has
+    // measured 2 % on a column pass, slm_capi.hip plan_create_on): a, b, d, tmp,
+    // tmp2, x (GD); then per side, W before H: twiddles, output order, and on a
+    // chirp-z side the chirp and bhat
+    int build(const PlanState& v) override {
+        const size_t bytes = (size_t)v.B * v.holo * sizeof(double2);
+        hipStream_t st = v.stream;
+        for (DevBuf<double2>* p : {&a, &b, &d, &tmp, &tmp2}) RC(p->need(bytes, st));
+        if (v.algo == SLM_ALGO_GD) RC(x.need(bytes, st));
+        RC(line_plan(tab_w, v.W, ch.chirp_all, &lw, &big_w, st));
+        RC(line_plan(tab_h, v.H, ch.chirp_all, &lh, &big_h, st));
+        return mr_roots(st);
+    }
+
+    // 1-D transforms of `lines` rows of the line plan's length
+    int pass(const mr::LineArgs& base, bool big, const double2* in, double2* out, long long lines, bool inverse,
+             hipStream_t st) {
+        if (lines > 0x7fffffffLL) return fail(SLM_ERR_UNSUPPORTED, "line transforms: too many lines");
+        mr::LineArgs la = base;
+        la.in = in;
+        la.out = out;
+        la.inverse = inverse ? 1 : 0;
+        if (mr::mr_line_launch(big, la, (int)lines, (size_t)la.pl.n * sizeof(double2), st))
+            return fail(SLM_ERR_HIP, "line transform launch failed");
+        return 0;
+    }
+
+    // rows -> transpose -> rows -> transpose
+    int transform(const PlanState& v, const double2* in, double2* out, bool inverse) override {
+        hipStream_t st = v.stream;
+        RC(pass(lw, big_w, in, tmp.p, (long long)v.B * v.H, inverse, st));
+        hipLaunchKernelGGL(k_transpose, dim3((v.W + 31) / 32, (v.H + 31) / 32, v.B), dim3(256), 0, st, tmp.p, tmp2.p,
+                           v.H, v.W);
+        RC(pass(lh, big_h, tmp2.p, tmp2.p, (long long)v.B * v.W, inverse, st));
+        hipLaunchKernelGGL(k_transpose, dim3((v.H + 31) / 32, (v.W + 31) / 32, v.B), dim3(256), 0, st, tmp2.p, out,
+                           v.W, v.H);
+        G_HIP(hipGetLastError());
+        return 0;
+    }
+
+    int field_c64(const PlanState& v, float2* out) override {
+        each(k_c128_to_c64, v.stream, (long long)v.B * v.holo, x.p, out);
+        G_HIP(hipGetLastError());
+        return 0;
+    }
+
+    // a = ifft2(sqrt T) in complex64: the GS cold start and the "fourier" guess of GD
+    int amp_ifft2(const PlanState& v, long long n) {
+        each(k_amp, v.stream, n, v.tgt, v.tt, d.p);
+        RC(transform(v, d.p, a.p, true));
+        each(k_round_c64, v.stream, n, a.p);
+        return 0;
+    }
+
+    int enqueue(PlanState& v, int loops, double tol, int checked, float wa, bool phase_set, bool field_set) override {
+        const long long n = (long long)v.B * v.holo;
+        const dim3 sgrid(v.nwg, v.B);
+        hipStream_t st = v.stream;
+        const double tol_or_none = checked ? tol : -1.0;
+        if (v.algo == SLM_ALGO_GS) {
+            if (phase_set)
+                each(k_warm, st, n, v.phase_in, b.p, v.ain, v.holo);
+            else
+                RC(amp_ifft2(v, n));
+            for (int i = 0; i < loops; ++i) {
+                if (i > 0 || !phase_set) each(k_unit, st, n, a.p, b.p, v.ain, v.holo);
+                RC(transform(v, b.p, b.p, false));  // C
+                hipLaunchKernelGGL(k_gs_project, sgrid, dim3(kGT), 0, st, b.p, v.tgt, v.tt, d.p, v.e_out, v.partials,
+                                   v.stop, i, checked, (checked || i + 1 == loops) ? 1 : 0, v.holo, v.nwg,
+                                   v.max_loops);
+                RC(transform(v, d.p, a.p, true));  // A = ifft2(D) * S
+                if (checked) reduce_iter(v, tol_or_none, i);
+            }
+            each(k_phase, st, n, a.p, v.phase_out);
+        } else {
+            if (field_set) {
+                each(k_c64_to_c128, st, n, v.field0, x.p);
+            } else {
+                RC(amp_ifft2(v, n));
+                each(k_fourier, st, n, a.p, x.p, v.ain, v.holo);
+            }
+            const double inv_s = 1.0 / (double)v.holo;
+            for (int i = 0; i < loops; ++i) {
+                each(k_gd_u, st, n, x.p, b.p, v.ain, v.holo);
+                RC(transform(v, b.p, b.p, false));  // F
+                hipLaunchKernelGGL(k_gd_stats, sgrid, dim3(kGT), 0, st, b.p, v.tgt, v.tt, v.e_out, v.partials, v.stop,
+                                   i, checked, (checked || i + 1 == loops) ? 1 : 0, v.holo, v.nwg, v.max_loops);
+                // this iteration's max |F|^2 (and, checked, its error against the tolerance)
+                reduce_iter(v, tol_or_none, i);
+                each(k_gd_grad, st, n, b.p, v.tgt, v.tt, v.stats, v.norm, d.p, wa, v.stop, i, checked, v.holo,
+                     v.max_loops);
+                RC(transform(v, d.p, a.p, true));  // g = ifft2(G) * S
+                each(k_gd_update, st, n, x.p, a.p, v.ain, v.lr, v.stop, i, checked, inv_s, v.holo);
+            }
+            each(k_phase, st, n, x.p, v.phase_out);
         }
-    if (mr::mr_set_roots(roots.data(), st)) return fail(SLM_ERR_HIP, "mixed radix: root table upload failed");
+        G_HIP(hipGetLastError());
+        return 0;
+    }
+};
+
+// ------------------------------------------------------------------------
+// 4. mixed radix and radix plans
+// ------------------------------------------------------------------------
+// Stockham twiddle table of a plan key (the float32 engine's layout,
+// slm_capi.hip get_twiddles: every pass after the first holds (R - 1) Ns
+// entries exp(-2 pi i j r / (Ns R)); a mixed plan appends the same for its
+// reversed pass order; float2 for the complex64 kernels) and the identity
+// order (natural in and out)
+int rz_plan_line(LineTables& t, int key, int prec, mr::LinePlan* pl, hipStream_t st) {
+    const RadixPlan& rp = kPlans[key];
+    std::vector<double> tw;
+    // the forward pass order, then (mixed plans) the reversed one the inverse runs
+    for (int rev = 0; rev < (plan_mixed(key) ? 2 : 1); ++rev) {
+        int ns = 1;
+        for (int k = 0; k < rp.npass; ++k) {
+            const int r_ = pass_radix(key, rev != 0, k);
+            if (ns > 1) {
+                const long long L = (long long)ns * r_;
+                for (int r = 1; r < r_; ++r)
+                    for (int j = 0; j < ns; ++j) {
+                        const long long q = ((long long)j * r) % L;
+                        const double ang = -2.0 * M_PI * (double)q / (double)L;
+                        tw.push_back(std::cos(ang));
+                        tw.push_back(std::sin(ang));
+                    }
+            }
+            ns *= r_;
+        }
+    }
+    if (tw.empty()) {
+        tw.push_back(1.0);
+        tw.push_back(0.0);
+    }
+    std::vector<int> rev(rp.n);
+    for (int e = 0; e < rp.n; ++e) rev[e] = e;
+    std::vector<float> twf(tw.begin(), tw.end());
+    const bool f32 = prec == PREC_F32;
+    RC(upload_pair(t.tw, f32 ? (const void*)twf.data() : (const void*)tw.data(),
+                   f32 ? twf.size() * sizeof(float) : tw.size() * sizeof(double), t.rev, rev.data(),
+                   rev.size() * sizeof(int), st));
+    pl->n = rp.n;
+    pl->np = 0;
+    pl->tw = static_cast<const double2*>(t.tw.p);
+    pl->rev = static_cast<const int*>(t.rev.p);
     return 0;
 }
 
+// Both back ends run an iteration as a column launch and a row launch on tiles
+// (mr::RowArgs / mr::ColArgs, mixed_radix.hpp); the radix plans put the same
+// contract on compile-time Stockham transforms (their line plans hold Stockham
+// twiddle tables and the identity order). Which of the two a plan is shows in
+// build(), row() and col() only.
+struct TiledEngine : AnySizeEngine {
+    using AnySizeEngine::AnySizeEngine;
+    mr::LinePlan pw, ph;      // row (length W) and column (length H) transforms
+    LineTables tab_w, tab_h;  // their twiddles and output orders
+    int cw_log2 = 0;          // mixed radix: ch.cw = 2^cw_log2 (the radix kernels take ch.cw itself)
+    DevBuf<float> ain_rev;    // a_in with rows in the row transform's digit-reversed order (has_ain)
+    DevBuf<float> tgt_blk;    // radix plans: the target as float in their B2 layout (rebuilt per run)
+
+    bool radix_plans() const { return ch.kind >= 4; }
+
+    // hipMalloc order (kept as it always was: the order of two allocations has
+    // measured 2 % on a column pass, slm_capi.hip plan_create_on): a, b, x (GD),
+    // ain_rev (a_in), tgt_blk (radix plans, either layout); then the row plan's
+    // twiddles and output order, then the column plan's
+    int build(const PlanState& v) override {
+        const size_t n = (size_t)v.B * v.holo;
+        hipStream_t st = v.stream;
+        RC(a.need(n * sizeof(double2), st));
+        RC(b.need(n * sizeof(double2), st));
+        if (v.algo == SLM_ALGO_GD) RC(x.need(n * sizeof(double2), st));
+        if (v.has_ain) RC(ain_rev.need((size_t)v.holo * sizeof(float), st));
+        if (radix_plans()) {
+            RC(tgt_blk.need(n * sizeof(float), st));
+            RC(rz_plan_line(tab_w, ch.rkey, ch.prec, &pw, st));
+            RC(rz_plan_line(tab_h, ch.ckey, ch.prec, &ph, st));
+        } else {
+            while ((1 << cw_log2) < ch.cw) ++cw_log2;
+            RC(mr_plan_line(tab_w, v.W, &pw, st));
+            RC(mr_plan_line(tab_h, v.H, &ph, st));
+            RC(mr_roots(st));
+        }
+        // the state is defined before any run (read_field of a fresh plan is refused upstream)
+        if (hipMemsetAsync(a.p, 0, n * sizeof(double2), st) != hipSuccess)
+            return fail(SLM_ERR_HIP, "%s: state initialisation failed", radix_plans() ? "radix c128" : "mixed radix");
+        return 0;
+    }
+
+    int row(const PlanState& v, int op, mr::RowArgs ra, int cls = SLM_KERNEL_OTHER) {
+        ra.pl = pw;
+        ra.B = v.B;
+        ra.H = v.H;
+        ra.W = v.W;
+        ra.rpw = ch.rpw;
+        ra.holo = v.holo;
+        ra.inv_s = 1.0 / (double)v.holo;
+        ra.ain = v.ain;
+        ra.ain_rev = v.ain ? ain_rev.p : nullptr;
+        ra.stop = v.stop;
+        const int grid = v.B * ((v.H + ch.rpw - 1) / ch.rpw);
+        const size_t lds = (size_t)ch.rpw * v.W * sizeof(double2);
+        Mark mk(v, cls);
+        if (radix_plans()) {
+            // an unchecked run's iterations before the last never take the phase branch
+            if (op == mr::RO_GS && !ra.checked && !ra.last) op = mr::RO_GS_MID;
+            if (rz::rz_row_launch(ch.rkey, ch.prec, ch.lay, op, ra, grid, v.stream))
+                return fail(SLM_ERR_HIP, "radix-plan row launch failed");
+            return 0;
+        }
+        if (mr::mr_row_launch(op, ch.big, ra, grid, lds, v.stream))
+            return fail(SLM_ERR_HIP, "mixed-radix row launch failed");
+        return 0;
+    }
+
+    int col(const PlanState& v, int op, mr::ColArgs ca, int cls = SLM_KERNEL_OTHER) {
+        ca.pl = ph;
+        ca.B = v.B;
+        ca.H = v.H;
+        ca.W = v.W;
+        ca.cw_log2 = cw_log2;
+        ca.nwg = ch.nwg;
+        ca.holo = v.holo;
+        ca.tgt = v.tgt;
+        ca.tgt_blk = tgt_blk.p;
+        ca.tt = v.tt;
+        ca.e_out = v.e_out;
+        ca.partials = v.partials;
+        ca.stop = v.stop;
+        ca.stats = v.stats;
+        ca.norm = v.norm;
+        ca.max_loops = v.max_loops;
+        const int grid = v.B * ch.nwg;
+        const size_t lds = ((size_t)v.H << cw_log2) * sizeof(double2);
+        Mark mk(v, cls);
+        if (radix_plans()) {
+            if (op == mr::CO_GD_GRAD && v.tt == TGT_U8) op = mr::CO_GD_GRAD_U8;
+            if (rz::rz_col_launch(ch.ckey, ch.prec, ch.lay, ch.cw, op, ca, grid, v.stream))
+                return fail(SLM_ERR_HIP, "radix-plan column launch failed");
+            return 0;
+        }
+        if (mr::mr_col_launch(op, ch.big, ca, grid, lds, v.stream))
+            return fail(SLM_ERR_HIP, "mixed-radix column launch failed");
+        return 0;
+    }
+
+    // a row launch into a, a column launch out of it
+    int transform(const PlanState& v, const double2* in, double2* out, bool inverse) override {
+        mr::RowArgs r;
+        r.in = in;
+        r.out = a.p;
+        RC(row(v, inverse ? mr::RO_INV : mr::RO_FWD, r));
+        mr::ColArgs c;
+        c.in = a.p;
+        c.out = out;
+        return col(v, inverse ? mr::CO_INV : mr::CO_FWD, c);
+    }
+
+    // The field x is kept with every row in the row transform's output order
+    // (k_c128_to_c64_rev; the identity on radix plans)
+    int field_c64(const PlanState& v, float2* out) override {
+        each(k_c128_to_c64_rev, v.stream, (long long)v.B * v.holo, x.p, out, pw.rev, v.W);
+        G_HIP(hipGetLastError());
+        return 0;
+    }
+
+    int enqueue(PlanState& v, int loops, double tol, int checked, float wa, bool phase_set, bool field_set) override {
+        const long long n = (long long)v.B * v.holo;
+        hipStream_t st = v.stream;
+        const double tol_or_none = checked ? tol : -1.0;
+        mr::RowArgs r;
+        mr::ColArgs c;
+        r.checked = c.checked = checked;
+        c.wa = wa;
+        if (ch.lay == rz::LAY_B2)  // the target in B2 (set_target may have changed it)
+            each(k_tgt_b2, st, n, v.tgt, v.tt, tgt_blk.p, v.H, v.W);
+        if (v.ain)  // the row passes read a_in in their digit-reversed order
+            each(k_ain_rev, st, v.holo, v.ain, ain_rev.p, pw.rev, v.W);
+        if (v.algo == SLM_ALGO_GS) {
+            // setup (src/algorithms.py:14-27): the warm start B = a_in exp(i phi), or
+            // A0 = ifft2(sqrt T) in complex64, B = a_in A0/|A0|; row-transformed into a
+            if (phase_set) {
+                r.phase_in = v.phase_in;
+                r.out = a.p;
+                RC(row(v, mr::RO_WARM, r));
+            } else {
+                c.out = b.p;
+                RC(col(v, mr::CO_AMP_INV, c));
+                r.in = b.p;
+                r.out = a.p;
+                RC(row(v, mr::RO_COLD, r));
+            }
+            for (int i = 0; i < loops; ++i) {
+                c.in = a.p;
+                c.out = b.p;
+                c.iter = i;
+                c.write_e = (checked || i + 1 == loops) ? 1 : 0;
+                RC(col(v, mr::CO_GS, c, SLM_KERNEL_COL_MAIN));
+                if (checked) reduce_iter(v, tol_or_none, i);
+                r.in = b.p;
+                r.out = a.p;
+                r.iter = i;
+                r.last = i + 1 == loops;
+                r.phase_out = v.phase_out;
+                RC(row(v, mr::RO_GS, r, SLM_KERNEL_ROW_MAIN));
+            }
+        } else {
+            // setup (make_initial_guess, src/algorithms.py:115-158): the host field, or
+            // the "fourier" guess a_in exp(i angle(ifft2(sqrt T)))
+            r.x = x.p;
+            if (field_set) {
+                r.field0 = v.field0;
+                r.out = a.p;
+                RC(row(v, mr::RO_GD_INIT, r));
+            } else {
+                c.out = b.p;
+                RC(col(v, mr::CO_AMP_INV, c));
+                r.in = b.p;
+                r.out = a.p;
+                RC(row(v, mr::RO_GD_FOURIER, r));
+            }
+            r.lr = v.lr;
+            for (int i = 0; i < loops; ++i) {
+                c.in = a.p;
+                c.iter = i;
+                c.write_e = (checked || i + 1 == loops) ? 1 : 0;
+                RC(col(v, mr::CO_GD_STATS, c, SLM_KERNEL_GD_STATS));
+                // this iteration's max |F|^2 (and, checked, its error against the tolerance)
+                reduce_iter(v, tol_or_none, i);
+                c.out = b.p;
+                RC(col(v, mr::CO_GD_GRAD, c, SLM_KERNEL_COL_MAIN));
+                r.in = b.p;
+                r.out = a.p;
+                r.iter = i;
+                r.last = i + 1 == loops;
+                RC(row(v, mr::RO_GD, r, SLM_KERNEL_ROW_MAIN));
+            }
+            each(k_phase_rev, st, n, x.p, v.phase_out, pw.rev, v.W);
+        }
+        G_HIP(hipGetLastError());
+        return 0;
+    }
+};
+
 // ------------------------------------------------------------------------
-// complex128 radix-plan back end (host side)
+// 5. the choice
 // ------------------------------------------------------------------------
+// $SLM_GENERIC_ENGINE: mr keeps a plan off the radix-plan kernels; bluestein
+// (alias: gemm, r05's name of that back end) sends every side through the line
+// transforms, chirp-z included
+enum Forced { FORCE_NONE, FORCE_MR, FORCE_LINES };
+Forced forced_back_end() {
+    const char* e = std::getenv("SLM_GENERIC_ENGINE");
+    if (e && (!std::strcmp(e, "bluestein") || !std::strcmp(e, "gemm"))) return FORCE_LINES;
+    return e && !std::strcmp(e, "mr") ? FORCE_MR : FORCE_NONE;
+}
+
+// Mixed-radix tiles of the two launches. A launch of `wgs` workgroups of `e`
+// elements on `cus` CUs that hold `occ` of them at once takes about rounds x
+// (workgroups per CU in a round) x e: so the rows per row tile / columns per
+// column tile minimise ceil(wgs / (cus occ)) * min(occ, ceil(wgs / cus)) * e (a
+// grid one workgroup too large for a round doubles the launch: 1080 rows in 540
+// two-row tiles on 512 slots did, 62.6 against ~35 us). Column tiles that tie
+// go to 2 columns (32-B row segments), then the narrower: 1080 x 1920 columns
+// in tiles of 2 measured 48.2 us against 58.0 in tiles of 1 and 55.0 in tiles
+// of 4 (profiles/r05/mr_tiles_s13.txt); row tiles that tie go to the wider.
+// $SLM_MR_RPW / $SLM_MR_CW override.
+void mr_tiling(int B, int H, int W, AnySizeChoice* t) {
+    const bool big = t->big;
+    int cw_log2 = 0;
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+        cus = 256;
+    auto cost = [&](long long wgs, int occ, long long e) {
+        const long long slots = (long long)cus * occ;
+        const long long rounds = (wgs + slots - 1) / slots;
+        const long long per = std::min<long long>(occ, (wgs + cus - 1) / cus);
+        return rounds * per * e;
+    };
+    long long best = -1;
+    for (int r = 1; r == 1 || (long long)r * W <= mr::kTileElems; r *= 2) {
+        if (r > 1 && r > H) break;
+        const int occ = mr::mr_row_occupancy(mr::RO_GS, big, (size_t)r * W * sizeof(double2));
+        if (occ < 1) continue;
+        const long long c = cost((long long)B * ((H + r - 1) / r), occ, (long long)r * W);
+        if (best < 0 || c <= best) {
+            best = c;
+            t->rpw = r;
+        }
+    }
+    best = -1;
+    for (int c : {1, 0, 2, 3, 4}) {  // tie order
+        if (c > 0 && (((long long)H << c) > mr::kTileElems || (1 << c) > 2 * W)) continue;
+        const int occ = mr::mr_col_occupancy(mr::CO_GS, big, ((size_t)H << c) * sizeof(double2));
+        if (occ < 1) continue;
+        const long long v = cost((long long)B * ((W + (1 << c) - 1) >> c), occ, (long long)H << c);
+        if (best < 0 || v < best) {
+            best = v;
+            cw_log2 = c;
+        }
+    }
+    if (const char* e = std::getenv("SLM_MR_RPW")) t->rpw = std::max(1, std::min(H, std::atoi(e)));
+    if (const char* e = std::getenv("SLM_MR_CW")) {
+        int c = 0;
+        while (c < 4 && (2 << c) <= std::atoi(e)) ++c;
+        cw_log2 = c;
+    }
+    t->cw = 1 << cw_log2;
+    t->nwg = (W + t->cw - 1) >> cw_log2;
+}
+
 // Plan key of one axis: both sides need a built radix plan (rz::key_built) at
 // the engine's precision; a 13-smooth panel side (plans.hpp variant 3,
 // complex64 only) has its one plan.
@@ -739,485 +1148,63 @@ int rz_layout(int algo, int H, int W, int prec) {
     return (algo == SLM_ALGO_GS && std::max(H, W) >= 4096) ? rz::LAY_RM : rz::LAY_B2;
 }
 
-struct RzChoice {
-    int rkey = -1, ckey = -1, cw = 0, lay = 0;
-};
-// complex64 radix kernels: GS only (GD's 500-iteration gradient loop keeps
-// complex128 state)
-bool rz_shape(int B, int H, int W, RzChoice* c, int algo, int prec) {
-    const char* e = std::getenv("SLM_GENERIC_ENGINE");
-    if (e && (!std::strcmp(e, "mr") || !std::strcmp(e, "gemm") || !std::strcmp(e, "bluestein"))) return false;
+// The radix-plan choice at `prec`, if the shape has one. Complex64 radix
+// kernels: GS only (GD's 500-iteration gradient loop keeps complex128 state,
+// DESIGN.md section 3)
+bool rz_shape(int B, int H, int W, int algo, int prec, AnySizeChoice* out) {
     if (prec == PREC_F32 && algo != SLM_ALGO_GS) return false;
+    AnySizeChoice c;
+    c.kind = prec == PREC_F32 ? 5 : 4;
+    c.prec = prec;
     const long long elems = (long long)B * H * W;
-    c->rkey = rz_key(W, elems, false, prec, algo);
-    c->ckey = rz_key(H, elems, true, prec, algo);
-    if (c->rkey < 0 || c->ckey < 0) return false;
-    c->cw = rz_cw_of(c->ckey, W, prec);
-    c->lay = rz_layout(algo, H, W, prec);
-    if (rz::key_panel(c->rkey) || rz::key_panel(c->ckey)) c->lay = rz::LAY_B2;  // panel keys: B2 only
-    const int rpw = rz::rz_row_rpw(c->rkey, c->lay);
-    return c->cw > 0 && rpw > 0 && H % rpw == 0 && W % 2 == 0;  // B2 panels (and the target copy)
-}
-
-// Stockham twiddle table of a plan key (the float32 engine's layout,
-// slm_capi.hip get_twiddles: every pass after the first holds (R - 1) Ns
-// entries exp(-2 pi i j r / (Ns R)); a mixed plan appends the same for its
-// reversed pass order; float2 for the complex64 kernels) and the identity
-// order (natural in and out)
-int rz_plan_line(GenericEngine* g, int key, mr::LinePlan* pl, hipStream_t st) {
-    const RadixPlan& rp = kPlans[key];
-    std::vector<double> tw;
-    // the forward pass order, then (mixed plans) the reversed one the inverse runs
-    for (int rev = 0; rev < (plan_mixed(key) ? 2 : 1); ++rev) {
-        int ns = 1;
-        for (int k = 0; k < rp.npass; ++k) {
-            const int r_ = pass_radix(key, rev != 0, k);
-            if (ns > 1) {
-                const long long L = (long long)ns * r_;
-                for (int r = 1; r < r_; ++r)
-                    for (int j = 0; j < ns; ++j) {
-                        const long long q = ((long long)j * r) % L;
-                        const double ang = -2.0 * M_PI * (double)q / (double)L;
-                        tw.push_back(std::cos(ang));
-                        tw.push_back(std::sin(ang));
-                    }
-            }
-            ns *= r_;
-        }
-    }
-    if (tw.empty()) {
-        tw.push_back(1.0);
-        tw.push_back(0.0);
-    }
-    std::vector<int> rev(rp.n);
-    for (int e = 0; e < rp.n; ++e) rev[e] = e;
-    std::vector<float> twf(tw.begin(), tw.end());
-    const bool f32 = g->prec == PREC_F32;
-    const size_t tw_bytes = f32 ? twf.size() * sizeof(float) : tw.size() * sizeof(double);
-    void *dtw = nullptr, *drev = nullptr;
-    if (hipMalloc(&dtw, tw_bytes) != hipSuccess) return fail(SLM_ERR_HIP, "radix plans: allocation");
-    g->tables.push_back(dtw);
-    if (hipMalloc(&drev, rev.size() * sizeof(int)) != hipSuccess) return fail(SLM_ERR_HIP, "radix plans: allocation");
-    g->tables.push_back(drev);
-    G_HIP(hipMemcpyAsync(dtw, f32 ? (const void*)twf.data() : (const void*)tw.data(), tw_bytes, hipMemcpyHostToDevice,
-                         st));
-    G_HIP(hipMemcpyAsync(drev, rev.data(), rev.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    G_HIP(hipStreamSynchronize(st));
-    pl->n = rp.n;
-    pl->np = 0;
-    pl->tw = static_cast<const double2*>(dtw);
-    pl->rev = static_cast<const int*>(drev);
-    return 0;
-}
-
-// a timed run's event pair around a launch (slm_plan_run_timed; the any-size
-// engine launches directly, so the events are recorded on the plan stream)
-struct Mark {
-    const PlanState& v;
-    std::pair<hipEvent_t, hipEvent_t>* ev = nullptr;
-    Mark(const PlanState& vv, int cls) : v(vv) {
-        if (v.timing && !v.timing->next(cls, &ev)) (void)hipEventRecord(ev->first, v.stream);
-    }
-    ~Mark() {
-        if (ev) (void)hipEventRecord(ev->second, v.stream);
-    }
-};
-
-int mr_row(GenericEngine* g, const PlanState& v, int op, mr::RowArgs a, int cls = SLM_KERNEL_OTHER) {
-    a.pl = g->pw;
-    a.B = v.B;
-    a.H = v.H;
-    a.W = v.W;
-    a.rpw = g->rpw;
-    a.holo = v.holo;
-    a.inv_s = 1.0 / (double)v.holo;
-    a.ain = v.ain;
-    a.ain_rev = v.ain ? g->ain_rev : nullptr;
-    a.stop = v.stop;
-    const int grid = v.B * ((v.H + g->rpw - 1) / g->rpw);
-    const size_t lds = (size_t)g->rpw * v.W * sizeof(double2);
-    Mark mk(v, cls);
-    if (g->rz) {
-        // an unchecked run's iterations before the last never take the phase branch
-        if (op == mr::RO_GS && !a.checked && !a.last) op = mr::RO_GS_MID;
-        if (rz::rz_row_launch(g->rkey, g->prec, g->rz_lay, op, a, grid, v.stream))
-            return fail(SLM_ERR_HIP, "radix-plan row launch failed");
-        return 0;
-    }
-    if (mr::mr_row_launch(op, g->big, a, grid, lds, v.stream))
-        return fail(SLM_ERR_HIP, "mixed-radix row launch failed");
-    return 0;
-}
-
-int mr_col(GenericEngine* g, const PlanState& v, int op, mr::ColArgs a, int cls = SLM_KERNEL_OTHER) {
-    a.pl = g->ph;
-    a.B = v.B;
-    a.H = v.H;
-    a.W = v.W;
-    a.cw_log2 = g->cw_log2;
-    a.nwg = g->nwg_col;
-    a.holo = v.holo;
-    a.tgt = v.tgt;
-    a.tgt_blk = g->tgt_blk;
-    a.tt = v.tt;
-    a.e_out = v.e_out;
-    a.partials = v.partials;
-    a.stop = v.stop;
-    a.stats = v.stats;
-    a.norm = v.norm;
-    a.max_loops = v.max_loops;
-    const int grid = v.B * g->nwg_col;
-    const size_t lds = ((size_t)v.H << g->cw_log2) * sizeof(double2);
-    Mark mk(v, cls);
-    if (g->rz) {
-        if (op == mr::CO_GD_GRAD && v.tt == TGT_U8) op = mr::CO_GD_GRAD_U8;
-        if (rz::rz_col_launch(g->ckey, g->prec, g->rz_lay, g->rz_cw, op, a, grid, v.stream))
-            return fail(SLM_ERR_HIP, "radix-plan column launch failed");
-        return 0;
-    }
-    if (mr::mr_col_launch(op, g->big, a, grid, lds, v.stream))
-        return fail(SLM_ERR_HIP, "mixed-radix column launch failed");
-    return 0;
-}
-
-// out = fft2 / unscaled ifft2 of in (device complex128 [B][H][W]; in may equal out)
-int mr_fft2(GenericEngine* g, const PlanState& v, const double2* in, double2* out, bool inverse) {
-    mr::RowArgs r;
-    r.in = in;
-    r.out = g->a;
-    if (int rc = mr_row(g, v, inverse ? mr::RO_INV : mr::RO_FWD, r)) return rc;
-    mr::ColArgs c;
-    c.in = g->a;
-    c.out = out;
-    return mr_col(g, v, inverse ? mr::CO_INV : mr::CO_FWD, c);
-}
-
-int mr_enqueue(GenericEngine* g, const PlanState& v, int loops, double tol, int checked, float wa, bool phase_set,
-               bool field_set) {
-    const long long n = (long long)v.B * v.holo;
-    const int grid = grid_of(n);
-    hipStream_t st = v.stream;
-    const double tol_or_none = checked ? tol : -1.0;
-    mr::RowArgs r;
-    mr::ColArgs c;
-    r.checked = c.checked = checked;
-    c.wa = wa;
-    if (g->rz && g->rz_lay == rz::LAY_B2)  // the target in B2 (set_target may have changed it)
-        hipLaunchKernelGGL(k_tgt_b2, dim3(grid), dim3(kGT), 0, st, v.tgt, v.tt, g->tgt_blk, v.H, v.W, n);
-    if (v.ain)  // the row passes read a_in in their digit-reversed order
-        hipLaunchKernelGGL(k_ain_rev, dim3(grid_of(v.holo)), dim3(kGT), 0, st, v.ain, g->ain_rev, g->pw.rev, v.W,
-                           v.holo);
-    if (v.algo == SLM_ALGO_GS) {
-        // setup (src/algorithms.py:14-27): the warm start B = a_in exp(i phi), or
-        // A0 = ifft2(sqrt T) in complex64, B = a_in A0/|A0|; row-transformed into a
-        if (phase_set) {
-            r.phase_in = v.phase_in;
-            r.out = g->a;
-            if (int rc = mr_row(g, v, mr::RO_WARM, r)) return rc;
-        } else {
-            c.out = g->b;
-            if (int rc = mr_col(g, v, mr::CO_AMP_INV, c)) return rc;
-            r.in = g->b;
-            r.out = g->a;
-            if (int rc = mr_row(g, v, mr::RO_COLD, r)) return rc;
-        }
-        for (int i = 0; i < loops; ++i) {
-            c.in = g->a;
-            c.out = g->b;
-            c.iter = i;
-            c.write_e = (checked || i + 1 == loops) ? 1 : 0;
-            if (int rc = mr_col(g, v, mr::CO_GS, c, SLM_KERNEL_COL_MAIN)) return rc;
-            if (checked) hipLaunchKernelGGL(k_reduce_iter, dim3(v.B), dim3(256), 0, st, stats_of(v, tol_or_none, i));
-            r.in = g->b;
-            r.out = g->a;
-            r.iter = i;
-            r.last = i + 1 == loops;
-            r.phase_out = v.phase_out;
-            if (int rc = mr_row(g, v, mr::RO_GS, r, SLM_KERNEL_ROW_MAIN)) return rc;
-        }
-    } else {
-        // setup (make_initial_guess, src/algorithms.py:115-158): the host field, or
-        // the "fourier" guess a_in exp(i angle(ifft2(sqrt T)))
-        r.x = g->x;
-        if (field_set) {
-            r.field0 = v.field0;
-            r.out = g->a;
-            if (int rc = mr_row(g, v, mr::RO_GD_INIT, r)) return rc;
-        } else {
-            c.out = g->b;
-            if (int rc = mr_col(g, v, mr::CO_AMP_INV, c)) return rc;
-            r.in = g->b;
-            r.out = g->a;
-            if (int rc = mr_row(g, v, mr::RO_GD_FOURIER, r)) return rc;
-        }
-        r.lr = v.lr;
-        for (int i = 0; i < loops; ++i) {
-            c.in = g->a;
-            c.iter = i;
-            c.write_e = (checked || i + 1 == loops) ? 1 : 0;
-            if (int rc = mr_col(g, v, mr::CO_GD_STATS, c, SLM_KERNEL_GD_STATS)) return rc;
-            // this iteration's max |F|^2 (and, checked, its error against the tolerance)
-            hipLaunchKernelGGL(k_reduce_iter, dim3(v.B), dim3(256), 0, st, stats_of(v, tol_or_none, i));
-            c.out = g->b;
-            if (int rc = mr_col(g, v, mr::CO_GD_GRAD, c, SLM_KERNEL_COL_MAIN)) return rc;
-            r.in = g->b;
-            r.out = g->a;
-            r.iter = i;
-            r.last = i + 1 == loops;
-            if (int rc = mr_row(g, v, mr::RO_GD, r, SLM_KERNEL_ROW_MAIN)) return rc;
-        }
-        hipLaunchKernelGGL(k_phase_rev, dim3(grid), dim3(kGT), 0, st, g->x, v.phase_out, g->pw.rev, v.W, n);
-    }
-    G_HIP(hipGetLastError());
-    return 0;
+    c.rkey = rz_key(W, elems, false, prec, algo);
+    c.ckey = rz_key(H, elems, true, prec, algo);
+    if (c.rkey < 0 || c.ckey < 0) return false;
+    c.cw = rz_cw_of(c.ckey, W, prec);
+    c.lay = rz_layout(algo, H, W, prec);
+    if (rz::key_panel(c.rkey) || rz::key_panel(c.ckey)) c.lay = rz::LAY_B2;  // panel keys: B2 only
+    c.rpw = rz::rz_row_rpw(c.rkey, c.lay);
+    if (!(c.cw > 0 && c.rpw > 0 && H % c.rpw == 0 && W % 2 == 0)) return false;  // B2 panels (and the target copy)
+    c.nwg = W / c.cw;
+    *out = c;
+    return true;
 }
 
 }  // namespace
 
-int generic_precision(int B, int H, int W, int algo, int prec) {
-    RzChoice rc;
-    return prec == PREC_F32 && rz_shape(B, H, W, &rc, algo, PREC_F32) ? PREC_F32 : PREC_F64;
-}
-
-int generic_nwg(int B, int H, int W, long long holo, int algo, int prec) {
-    RzChoice rc;
-    if (rz_shape(B, H, W, &rc, algo, generic_precision(B, H, W, algo, prec))) return W / rc.cw;
-    if (mr_shape_ok(H, W)) {
-        const MrTiling t = mr_tiling(B, H, W);
-        return (W + (1 << t.cw_log2) - 1) >> t.cw_log2;
+// Radix plans where both sides have one at the precision (complex64 if float32
+// was asked for and GS can run it, else complex128); else mixed radix where both
+// sides factor into 2 .. 13; else line transforms.
+AnySizeChoice generic_choose(int B, int H, int W, int algo, int prec) {
+    AnySizeChoice c;
+    const Forced forced = forced_back_end();
+    if (forced == FORCE_NONE &&
+        ((prec == PREC_F32 && rz_shape(B, H, W, algo, PREC_F32, &c)) || rz_shape(B, H, W, algo, PREC_F64, &c)))
+        return c;
+    std::vector<int> r;
+    if (forced != FORCE_LINES && mr_radices(H, r) && mr_radices(W, r)) {
+        c.kind = 3;
+        c.big = big_radix(H) || big_radix(W);
+        mr_tiling(B, H, W, &c);
+        return c;
     }
-    return (int)std::max<long long>(1, std::min<long long>(1024, holo / (kGT * 8)));
+    c.chirp_all = forced == FORCE_LINES;
+    c.nwg = (int)std::max<long long>(1, std::min<long long>(1024, (long long)H * W / (kGT * 8)));
+    return c;
 }
 
-int GenericEngine::generic_info(int info[8]) const {
-    const GenericEngine* g = this;
-    info[0] = kind();
-    info[1] = g->prec;
-    info[2] = g->rz ? g->rkey : -1;
-    info[3] = g->rz ? g->ckey : -1;
-    info[4] = g->mr ? g->rpw : 1;
-    info[5] = g->rz ? g->rz_cw : g->mr ? 1 << g->cw_log2 : 1;
-    info[6] = g->rz ? g->rz_lay : 0;
-    info[7] = g->mr ? g->nwg_col : 0;
-    return 0;
-}
-
-GenericEngine::~GenericEngine() {
-    GenericEngine* g = this;
-    for (void* p : {(void*)g->a, (void*)g->b, (void*)g->d, (void*)g->x, (void*)g->tmp, (void*)g->tmp2})
-        if (p) (void)hipFree(p);
-    for (void* p : g->tables)
-        if (p) (void)hipFree(p);
-    if (g->ain_rev) (void)hipFree(g->ain_rev);
-    if (g->tgt_blk) (void)hipFree(g->tgt_blk);
-}
-
-int generic_create(const PlanState& v, Engine** out) {
+int generic_create(const PlanState& v, const AnySizeChoice& c, Engine** out) {
     *out = nullptr;
-    GenericEngine* g = new GenericEngine();
-    auto fail_free = [&](int rc) {
-        delete g;
-        return rc;
-    };
-    const size_t n = (size_t)v.B * v.holo;
-    auto alloc = [&](double2** p, size_t count) {
-        return hipMalloc((void**)p, count * sizeof(double2)) == hipSuccess;
-    };
-    RzChoice rc;
-    const int prec = generic_precision(v.B, v.H, v.W, v.algo, v.prec);
-    if (rz_shape(v.B, v.H, v.W, &rc, v.algo, prec)) {  // radix plans: the mixed-radix buffers, Stockham tables
-        g->mr = g->rz = true;
-        g->prec = prec;
-        g->rkey = rc.rkey;
-        g->ckey = rc.ckey;
-        g->rz_cw = rc.cw;
-        g->rz_lay = rc.lay;
-        g->nwg_col = v.W / rc.cw;
-        g->rpw = rz::rz_row_rpw(rc.rkey, rc.lay);
-        if (g->nwg_col != v.nwg) return fail_free(fail(SLM_ERR_STATE, "radix c128: partial-slab mismatch"));
-        if (!alloc(&g->a, n) || !alloc(&g->b, n) || (v.algo == SLM_ALGO_GD && !alloc(&g->x, n)) ||
-            (v.has_ain && hipMalloc((void**)&g->ain_rev, (size_t)v.holo * sizeof(float)) != hipSuccess) ||
-            hipMalloc((void**)&g->tgt_blk, n * sizeof(float)) != hipSuccess)
-            return fail_free(fail(SLM_ERR_HIP, "radix c128: device allocation failed"));
-        if (int e = rz_plan_line(g, rc.rkey, &g->pw, v.stream)) return fail_free(e);
-        if (int e = rz_plan_line(g, rc.ckey, &g->ph, v.stream)) return fail_free(e);
-        if (hipMemsetAsync(g->a, 0, n * sizeof(double2), v.stream) != hipSuccess)
-            return fail_free(fail(SLM_ERR_HIP, "radix c128: state initialisation failed"));
-        *out = g;
-        return 0;
-    }
-    if (mr_shape_ok(v.H, v.W)) {  // mixed radix: two state buffers (+ the GD field), line plans
-        g->mr = true;
-        g->big = mr_big(v.H, v.W);
-        const MrTiling t = mr_tiling(v.B, v.H, v.W);
-        g->cw_log2 = t.cw_log2;
-        g->nwg_col = (v.W + (1 << g->cw_log2) - 1) >> g->cw_log2;
-        g->rpw = t.rpw;
-        if (g->nwg_col != v.nwg) return fail_free(fail(SLM_ERR_STATE, "mixed radix: partial-slab mismatch"));
-        if (!alloc(&g->a, n) || !alloc(&g->b, n) || (v.algo == SLM_ALGO_GD && !alloc(&g->x, n)) ||
-            (v.has_ain && hipMalloc((void**)&g->ain_rev, (size_t)v.holo * sizeof(float)) != hipSuccess))
-            return fail_free(fail(SLM_ERR_HIP, "mixed radix: device allocation failed"));
-        if (int rc = mr_plan_line(g, v.W, &g->pw, v.stream)) return fail_free(rc);
-        if (int rc = mr_plan_line(g, v.H, &g->ph, v.stream)) return fail_free(rc);
-        if (int rc = mr_roots(v.stream)) return fail_free(rc);
-        // the state is defined before any run (read_field of a fresh plan is refused upstream)
-        if (hipMemsetAsync(g->a, 0, n * sizeof(double2), v.stream) != hipSuccess)
-            return fail_free(fail(SLM_ERR_HIP, "mixed radix: state initialisation failed"));
-        *out = g;
-        return 0;
-    }
-    if (!alloc(&g->a, n) || !alloc(&g->b, n) || !alloc(&g->d, n) || !alloc(&g->tmp, n) || !alloc(&g->tmp2, n) ||
-        (v.algo == SLM_ALGO_GD && !alloc(&g->x, n)))
-        return fail_free(fail(SLM_ERR_HIP, "line transforms: device allocation failed"));
-    const bool chirp_all = mr_forced_lines();
-    if (int rc = line_plan(g, v.W, chirp_all, &g->lw, &g->big_w, v.stream)) return fail_free(rc);
-    if (int rc = line_plan(g, v.H, chirp_all, &g->lh, &g->big_h, v.stream)) return fail_free(rc);
-    if (int rc = mr_roots(v.stream)) return fail_free(rc);
-    *out = g;
-    return 0;
-}
-
-int GenericEngine::enqueue(PlanState& v, int loops, double tol, int checked, float wa, bool phase_set,
-                           bool field_set) {
-    GenericEngine* g = this;
-    if (g->mr) return mr_enqueue(g, v, loops, tol, checked, wa, phase_set, field_set);
-    const long long n = (long long)v.B * v.holo;
-    const int grid = grid_of(n);
-    const dim3 sgrid(v.nwg, v.B);
-    hipStream_t st = v.stream;
-    const double tol_or_none = checked ? tol : -1.0;  // k_reduce_iter sets stop flags for checked runs only
-    if (v.algo == SLM_ALGO_GS) {
-        if (phase_set) {
-            hipLaunchKernelGGL(k_warm, dim3(grid), dim3(kGT), 0, st, v.phase_in, g->b, v.ain, v.holo, n);
-        } else {
-            hipLaunchKernelGGL(k_amp, dim3(grid), dim3(kGT), 0, st, v.tgt, v.tt, g->d, n);
-            if (int rc = dft2(g, v, g->d, g->a, true)) return rc;
-            hipLaunchKernelGGL(k_round_c64, dim3(grid), dim3(kGT), 0, st, g->a, n);
-        }
-        for (int i = 0; i < loops; ++i) {
-            if (i > 0 || !phase_set) hipLaunchKernelGGL(k_unit, dim3(grid), dim3(kGT), 0, st, g->a, g->b, v.ain, v.holo, n);
-            if (int rc = dft2(g, v, g->b, g->b, false)) return rc;  // C
-            hipLaunchKernelGGL(k_gs_project, sgrid, dim3(kGT), 0, st, g->b, v.tgt, v.tt, g->d, v.e_out, v.partials,
-                               v.stop, i, checked, (checked || i + 1 == loops) ? 1 : 0, v.holo, v.nwg, v.max_loops);
-            if (int rc = dft2(g, v, g->d, g->a, true)) return rc;  // A = ifft2(D) * S
-            if (checked)
-                hipLaunchKernelGGL(k_reduce_iter, dim3(v.B), dim3(256), 0, st, stats_of(v, tol_or_none, i));
-        }
-        hipLaunchKernelGGL(k_phase, dim3(grid), dim3(kGT), 0, st, g->a, v.phase_out, n);
-    } else {
-        if (field_set) {
-            hipLaunchKernelGGL(k_c64_to_c128, dim3(grid), dim3(kGT), 0, st, v.field0, g->x, n);
-        } else {
-            hipLaunchKernelGGL(k_amp, dim3(grid), dim3(kGT), 0, st, v.tgt, v.tt, g->d, n);
-            if (int rc = dft2(g, v, g->d, g->a, true)) return rc;
-            hipLaunchKernelGGL(k_round_c64, dim3(grid), dim3(kGT), 0, st, g->a, n);
-            hipLaunchKernelGGL(k_fourier, dim3(grid), dim3(kGT), 0, st, g->a, g->x, v.ain, v.holo, n);
-        }
-        const double inv_s = 1.0 / (double)v.holo;
-        for (int i = 0; i < loops; ++i) {
-            hipLaunchKernelGGL(k_gd_u, dim3(grid), dim3(kGT), 0, st, g->x, g->b, v.ain, v.holo, n);
-            if (int rc = dft2(g, v, g->b, g->b, false)) return rc;  // F
-            hipLaunchKernelGGL(k_gd_stats, sgrid, dim3(kGT), 0, st, g->b, v.tgt, v.tt, v.e_out, v.partials, v.stop, i,
-                               checked, (checked || i + 1 == loops) ? 1 : 0, v.holo, v.nwg, v.max_loops);
-            // this iteration's max |F|^2 (and, checked, its error against the tolerance)
-            hipLaunchKernelGGL(k_reduce_iter, dim3(v.B), dim3(256), 0, st, stats_of(v, tol_or_none, i));
-            hipLaunchKernelGGL(k_gd_grad, dim3(grid), dim3(kGT), 0, st, g->b, v.tgt, v.tt, v.stats, v.norm, g->d, wa,
-                               v.stop, i, checked, v.holo, v.max_loops, n);
-            if (int rc = dft2(g, v, g->d, g->a, true)) return rc;  // g = ifft2(G) * S
-            hipLaunchKernelGGL(k_gd_update, dim3(grid), dim3(kGT), 0, st, g->x, g->a, v.ain, v.lr, v.stop, i, checked,
-                               inv_s, v.holo, n);
-        }
-        hipLaunchKernelGGL(k_phase, dim3(grid), dim3(kGT), 0, st, g->x, v.phase_out, n);
-    }
-    G_HIP(hipGetLastError());
-    return 0;
-}
-
-int GenericEngine::field_c64(const PlanState& v, float2* out) {
-    GenericEngine* g = this;
-    if (!g->x) return fail(SLM_ERR_STATE, "the field is the state of GD plans");
-    const long long n = (long long)v.B * v.holo;
-    if (g->mr)  // rows in digit-reversed order
-        hipLaunchKernelGGL(k_c128_to_c64_rev, dim3(grid_of(n)), dim3(kGT), 0, v.stream, g->x, out, g->pw.rev, v.W, n);
+    std::unique_ptr<AnySizeEngine> e;
+    if (c.kind == 2)
+        e.reset(new LinesEngine(c));
     else
-        hipLaunchKernelGGL(k_c128_to_c64, dim3(grid_of(n)), dim3(kGT), 0, v.stream, g->x, out, n);
-    G_HIP(hipGetLastError());
+        e.reset(new TiledEngine(c));
+    RC(e->build(v));
+    *out = e.release();
     return 0;
 }
 
-int GenericEngine::fft2_c64(const PlanState& v, const float2* in, float2* out, int inverse) {
-    GenericEngine* g = this;
-    const long long n = (long long)v.B * v.holo;
-    if (g->prec == PREC_F32)  // complex64 radix kernels: straight on the caller's buffers
-        return mr_fft2(g, v, reinterpret_cast<const double2*>(in), reinterpret_cast<double2*>(out), inverse != 0);
-    hipLaunchKernelGGL(k_c64_to_c128, dim3(grid_of(n)), dim3(kGT), 0, v.stream, in, g->b, n);
-    if (int rc = g->mr ? mr_fft2(g, v, g->b, g->b, inverse != 0) : dft2(g, v, g->b, g->b, inverse != 0)) return rc;
-    hipLaunchKernelGGL(k_c128_to_c64, dim3(grid_of(n)), dim3(kGT), 0, v.stream, g->b, out, n);
-    G_HIP(hipGetLastError());
-    return 0;
-}
-
-int GenericEngine::intensity(PlanState& v) {
-    GenericEngine* g = this;
-    const float* phase = v.phase_in;
-    float* out = v.e_out;
-    const long long n = (long long)v.B * v.holo;
-    if (g->prec == PREC_F32) {
-        float2* b = reinterpret_cast<float2*>(g->b);
-        hipLaunchKernelGGL(k_phase_exp_c64, dim3(grid_of(n)), dim3(kGT), 0, v.stream, phase, b, n);
-        if (int rc = mr_fft2(g, v, g->b, g->b, false)) return rc;
-        hipLaunchKernelGGL(k_abs2_c64, dim3(grid_of(n)), dim3(kGT), 0, v.stream, b, out, n);
-        G_HIP(hipGetLastError());
-        return 0;
-    }
-    hipLaunchKernelGGL(k_phase_exp, dim3(grid_of(n)), dim3(kGT), 0, v.stream, phase, g->b, n);
-    if (int rc = g->mr ? mr_fft2(g, v, g->b, g->b, false) : dft2(g, v, g->b, g->b, false)) return rc;
-    hipLaunchKernelGGL(k_abs2, dim3(grid_of(n)), dim3(kGT), 0, v.stream, g->b, out, n);
-    G_HIP(hipGetLastError());
-    return 0;
-}
-
-int GenericEngine::fft2_z(PlanState& v, const double2* in, double2* out, int inverse) {
-    GenericEngine* g = this;
-    if (g->prec != PREC_F64) return fail(SLM_ERR_STATE, "fft2_c128 on a complex64 engine");
-    return g->mr ? mr_fft2(g, v, in, out, inverse != 0) : dft2(g, v, in, out, inverse != 0);
-}
-
-int GenericEngine::land_field(PlanState& v, const float* field) {
-    HIP_TRY(hipMemcpyAsync(v.field0, field, (size_t)v.B * v.holo * sizeof(float2), hipMemcpyHostToDevice, v.stream));
-    return 0;
-}
-
-int GenericEngine::read_field(PlanState& v, bool fresh, float* field) {
-    if (!fresh) RC(field_c64(v, v.xa));
-    return copy_sync(field, fresh ? v.field0 : v.xa, (size_t)v.B * v.holo * sizeof(float2), hipMemcpyDeviceToHost,
-                     v.stream);
-}
-
-// row-major in place through the plan's staging buffer
-int GenericEngine::fft2(PlanState& v, const float* in, float* out, int inverse) {
-    const size_t bytes = (size_t)v.B * v.holo * sizeof(float2);
-    hipError_t e = hipMemcpyAsync(v.xa, in, bytes, hipMemcpyHostToDevice, v.stream);
-    if (e != hipSuccess) return fail(SLM_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
-    RC(fft2_c64(v, v.xa, v.xa, inverse));
-    return copy_sync(out, v.xa, bytes, hipMemcpyDeviceToHost, v.stream);
-}
-
-long long GenericEngine::kernel_bytes(const PlanState& v, int cls) const {
-    if (kind() == 2) return 0;  // line transforms: no column / row kernel classes
-    // mixed radix / radix plans, complex128 state (complex64: z = 8): column pass
-    // in z + T + out z (GD statistics: in + T); row pass in z + out z (+ a_in)
-    // (+ GD field read and write 2z)
-    const long long px = (long long)v.B * v.holo;
-    const long long tb = v.tt == SLM_TGT_U8 ? 1 : 4;
-    const long long ab = v.has_ain ? 4 : 0;
-    const long long z = v.prec == PREC_F32 ? 8 : 16;
-    switch (cls) {
-        case SLM_KERNEL_COL_MAIN: return px * (2 * z + tb);
-        case SLM_KERNEL_ROW_MAIN: return px * (2 * z + ab + (v.algo == SLM_ALGO_GD ? 2 * z : 0));
-        case SLM_KERNEL_GD_STATS: return px * (z + tb);
-        default: return 0;
-    }
-}
+const AnySizeChoice& generic_choice(const Engine& e) { return static_cast<const AnySizeEngine&>(e).ch; }
 
 }  // namespace slm

@@ -9,28 +9,45 @@
 // chirp-z over a mixed-radix length) plus element-wise kernels. slm_capi.hip
 // owns the plan's buffers (plan.hpp PlanState); this engine owns its work
 // buffers and line plans.
+//
+// Which back end, at which precision and on which tiles is decided once, by
+// generic_choose; generic_create builds what that choice says and nothing is
+// chosen again afterwards.
 #pragma once
 #include "plan.hpp"
 
 namespace slm {
 
-// statistics blocks per hologram (the partials' nwg): column tiles of the
-// mixed-radix / radix-plan back ends, element chunks of the line-transform one
-int generic_nwg(int B, int H, int W, long long holo, int algo = 0, int prec = 1);
-// the precision a plan of this shape, algorithm and requested precision runs
-// at: PREC_F32 takes the complex64 radix kernels where both sides have one
-// (GS only), else the engine runs in float64
-int generic_precision(int B, int H, int W, int algo, int prec);
-// The any-size engine of s (shape, algorithm, s.prec as generic_precision
-// reports it, s.nwg as generic_nwg does; tables upload on s.stream). Its codes
-// (slm_plan_engine): 2 line transforms (chirp-z), 3 mixed radix, 4 complex128
-// radix plans, 5 complex64 radix plans. Its generic_info is the geometry it
-// was created with (slm_plan_generic_info, slm_hip.h): info[0] = code,
-// [1] = precision, [2] / [3] = row / column plan key (-1 off the radix-plan
-// back ends), [4] = rows per row tile, [5] = columns per column tile,
-// [6] = state layout (radix_c128.hpp LAY_RM 0 / LAY_B2 1; 0 = row-major off
-// the radix-plan back ends), [7] = column workgroups per hologram. The
-// line-transform back end has no tiles: [4] = [5] = 1, [7] = 0.
-int generic_create(const PlanState& s, Engine** out);
+// What a plan of one shape, algorithm and requested precision runs on. The
+// members are slm_plan_generic_info's (slm_hip.h): info[0] = kind,
+// [1] = prec, [2] / [3] = rkey / ckey, [4] = rpw, [5] = cw, [6] = lay,
+// [7] = column workgroups per hologram (nwg; 0 on line transforms).
+struct AnySizeChoice {
+    // the back end, as slm_plan_engine reports it: 2 line transforms (chirp-z),
+    // 3 mixed radix, 4 complex128 radix plans, 5 complex64 radix plans
+    int kind = 2;
+    // the precision the plan runs at: SLM_PRECISION_F32 only on the complex64
+    // radix kernels (both sides have one, GS only), else float64
+    int prec = SLM_PRECISION_F64;
+    // statistics blocks per hologram (PlanState::nwg, the partials' tiling):
+    // column tiles of the tiled back ends, element chunks of the line transforms
+    int nwg = 0;
+    int rkey = -1, ckey = -1;  // radix plans: plan keys (plans.hpp) of the row / column transforms
+    int rpw = 1;               // rows per row tile (1 on line transforms: no tiles)
+    int cw = 1;                // columns per column tile
+    int lay = 0;               // state layout between the passes (radix_c128.hpp LAY_RM 0 / LAY_B2 1); 0 = row-major
+    bool big = false;          // mixed radix: a radix outside mr::small_radix in either plan (7, 11, 13)
+    bool chirp_all = false;    // line transforms forced ($SLM_GENERIC_ENGINE=bluestein): chirp-z on every side
+};
+
+// The choice for a shape, algorithm and requested precision. Reads
+// $SLM_GENERIC_ENGINE, $SLM_RZ_* and $SLM_MR_* and queries the tile kernels'
+// occupancy (mixed radix), all of it here and nowhere else.
+AnySizeChoice generic_choose(int B, int H, int W, int algo, int prec);
+// The any-size engine that `c` describes, for the plan s (s.prec = c.prec and
+// s.nwg = c.nwg are the caller's to set; tables upload on s.stream).
+int generic_create(const PlanState& s, const AnySizeChoice& c, Engine** out);
+// the choice an any-size engine was created with
+const AnySizeChoice& generic_choice(const Engine& e);
 
 }  // namespace slm

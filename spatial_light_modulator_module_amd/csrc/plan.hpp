@@ -37,7 +37,9 @@ struct EventPool {
 // its own layout: the fused engine keeps tgt and field0 blocked).
 struct PlanState {
     int algo = 0, B = 0, H = 0, W = 0, tt = 1, has_ain = 0, max_loops = 0;
-    int nwg = 0;  // statistics blocks per hologram (the partials' tiling), the engine's choice
+    // statistics blocks per hologram (the partials' tiling): fused_create's pick,
+    // or AnySizeChoice::nwg (generic.hpp) of the engine the plan has
+    int nwg = 0;
     // arithmetic the engine runs (SLM_PRECISION_*); parity at both: tests/test_gpu_precision.py
     int prec = SLM_PRECISION_F32;
     int device = 0;

@@ -1,6 +1,7 @@
 // Error and device plumbing shared by the host translation units of
 // libslm_hip.so (defined in slm_capi.hip): the thread-local error text behind
-// slm_last_error, the process's current device, and the try-macros.
+// slm_last_error, the process's current device, the try-macros, and the owning
+// device buffer (DevBuf) of the trap lists and the any-size engine.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,3 +46,34 @@ int dev_alloc(T** ptr, size_t bytes) {
         int rc_ = (x);        \
         if (rc_) return rc_;  \
     } while (0)
+
+namespace slm {
+
+// an owning device buffer that only grows (non-copyable, freed with its owner)
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;  // bytes
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+    // at least `bytes`; work on `st` may still read a live buffer, so the stream is waited for before
+    // it is freed. The buffer is empty if the allocation fails.
+    int need(size_t bytes, hipStream_t st) {
+        if (bytes <= cap) return 0;
+        if (p) {
+            if (hipStreamSynchronize(st) != hipSuccess) return slm::fail(SLM_ERR_HIP, "hipStreamSynchronize failed");
+            (void)hipFree(p);
+        }
+        p = nullptr;
+        cap = 0;
+        RC(slm::dev_alloc(&p, bytes));
+        cap = bytes;
+        return 0;
+    }
+};
+
+}  // namespace slm

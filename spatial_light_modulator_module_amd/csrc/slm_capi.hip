@@ -305,15 +305,18 @@ int plan_create_on(int device, int algo, int batch, int height, int width, int t
     // X ahead of the engine's Y: the 1024^2 column pass measured 2 % slower with the two the other way round
     RC(dev_alloc(&s.xa, n * sizeof(float2)));
     int max_nwg = 0;  // the partials hold the finest tiling of both precisions
+    AnySizeChoice choice;
     if (p->any_size) {
         // float32 GS (float32 targets unless $SLM_PRECISION) on the complex64
         // radix kernels where both sides have one (13-smooth panels, e.g.
         // 1080 x 1920), float64 otherwise and always under $SLM_ENGINE=float64
-        s.prec = generic_precision(batch, height, width, algo, forced64 ? PREC_F64 : s.prec);
-        s.nwg = generic_nwg(batch, height, width, s.holo, algo, s.prec);
+        const int asked = forced64 ? PREC_F64 : s.prec;
+        choice = generic_choose(batch, height, width, algo, asked);
+        s.prec = choice.prec;
+        s.nwg = choice.nwg;
         // slm_plan_set_precision may switch engines: partials for either tiling
-        max_nwg = std::max(generic_nwg(batch, height, width, s.holo, algo, PREC_F32),
-                           generic_nwg(batch, height, width, s.holo, algo, PREC_F64));
+        const int other = asked == PREC_F32 ? PREC_F64 : PREC_F32;
+        max_nwg = std::max(choice.nwg, generic_choose(batch, height, width, algo, other).nwg);
     } else {
         RC(fused_create(s, &p->eng, &max_nwg));
     }
@@ -333,7 +336,7 @@ int plan_create_on(int device, int algo, int batch, int height, int width, int t
     RC(dev_alloc(&s.normf, (size_t)batch * sizeof(float)));
     RC(dev_alloc(&s.sum_t2, (size_t)batch * sizeof(double)));
     RC(dev_alloc(&p->ts_part, (size_t)batch * ts_blocks(s.holo) * 2 * sizeof(double)));
-    if (p->any_size) RC(generic_create(s, &p->eng));
+    if (p->any_size) RC(generic_create(s, choice, &p->eng));
     *out = guard.release();
     return 0;
 }
@@ -342,7 +345,7 @@ int plan_create_on(int device, int algo, int batch, int height, int width, int t
 // drop-in's plans: move_traps.update_hologram calls it for every non-blank
 // image of the interactive trap loop, which rebuilt stream, buffers, line
 // plans and tables each time before r06. A few shapes are kept (oldest out);
-// slm_release_caches frees them (algorithms.clear_plans). generic_create reads
+// slm_release_caches frees them (algorithms.clear_plans). generic_choose reads
 // the engine and geometry overrides from the environment, so an entry also
 // keeps their values at its creation: a call under other values builds its own.
 struct C128Entry {
@@ -363,7 +366,8 @@ void c128_free(C128Entry& e) {
     e = C128Entry();
 }
 
-// the environment generic_create's choices depend on (generic.hip)
+// the environment generic_choose (generic.hip) reads: a hit skips the choice,
+// so the cache is looked up by the knobs' text, not by their outcome
 std::string c128_knobs() {
     std::string s;
     for (const char* name : {"SLM_ENGINE", "SLM_GENERIC_ENGINE", "SLM_RZ_PLAN", "SLM_RZ_ROW_PLAN", "SLM_RZ_COL_PLAN",
@@ -397,15 +401,16 @@ int c128_entry(int batch, int height, int width, C128Entry** out) {
     s.W = width;
     s.holo = (long long)height * width;
     s.max_loops = 1;
-    s.prec = PREC_F64;
-    s.nwg = generic_nwg(batch, height, width, s.holo, SLM_ALGO_GS, PREC_F64);
+    const AnySizeChoice choice = generic_choose(batch, height, width, SLM_ALGO_GS, PREC_F64);
+    s.prec = choice.prec;
+    s.nwg = choice.nwg;
     s.device = g_device;
     int rc = 0;
     if (hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess)
         rc = fail(SLM_ERR_HIP, "fft2_c128: stream creation failed");
     const size_t bytes = (size_t)batch * s.holo * sizeof(double2);
     if (!rc && hipMalloc(&e.buf, bytes) != hipSuccess) rc = fail(SLM_ERR_HIP, "fft2_c128: allocation of %zu bytes", bytes);
-    if (!rc) rc = generic_create(s, &e.eng);
+    if (!rc) rc = generic_create(s, choice, &e.eng);
     if (rc) {
         c128_free(e);
         return rc;
@@ -546,21 +551,22 @@ int slm_plan_set_precision(slm_plan* p, int precision) {
         return e->set_precision(s, precision);
     }
     // any-size engine: rebuilt when the precision it runs at changes
-    const int prec = generic_precision(s.B, s.H, s.W, s.algo, precision);
-    if (prec == s.prec) return 0;
+    const AnySizeChoice choice = generic_choose(s.B, s.H, s.W, s.algo, precision);
+    if (choice.prec == s.prec) return 0;
     HIP_TRY(hipStreamSynchronize(s.stream));
     RC(drop_graph(p));
-    const int old_prec = s.prec, old_nwg = s.nwg;
+    const AnySizeChoice old = generic_choice(*e);
+    auto rebuild = [&](const AnySizeChoice& c) {
+        s.prec = c.prec;
+        s.nwg = c.nwg;
+        return generic_create(s, c, &p->eng);
+    };
     delete p->eng;
     p->eng = nullptr;
-    s.prec = prec;
-    s.nwg = generic_nwg(s.B, s.H, s.W, s.holo, s.algo, prec);
-    const int rc = generic_create(s, &p->eng);
+    const int rc = rebuild(choice);
     if (rc) {  // keep a usable plan: the engine it had (its error stays the reported one)
-        s.prec = old_prec;
-        s.nwg = old_nwg;
         const std::string msg = slm_last_error();
-        if (generic_create(s, &p->eng)) p->eng = nullptr;
+        if (rebuild(old)) p->eng = nullptr;
         return fail(rc, "%s", msg.c_str());
     }
     return 0;

@@ -43,7 +43,7 @@
 // launches of the frame return at once on it, and the superposition of that
 // very iteration also stores the float32 phase and the quantised uint8 frame.
 //
-// Host side: every device buffer is a DevBuf; a list's four tables are one
+// Host side: every device buffer is a DevBuf (runtime.hpp); a list's four tables are one
 // launch (launch_tables), for slm_spots_set_traps and for a frame alike; and
 // run_frame issues the iterations a Frame describes: a run is the handle's own
 // buffers without a stop word (own_frame), a trajectory one slice per frame.
@@ -484,35 +484,9 @@ __global__ void __launch_bounds__(kFieldsThreads) spot_superpose_kernel(Superpos
 int grid_for(long long n) { return (int)std::min<long long>(8192, (n + 255) / 256); }
 int padded_traps(int m) { return (m + kTile - 1) / kTile * kTile; }
 
-// an owning device buffer that only grows (non-copyable, freed with its owner)
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;  // bytes
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    // at least `bytes`; work on `st` may still read a live buffer, so the stream is waited for before
-    // it is freed. The buffer is empty if the allocation fails.
-    int need(size_t bytes, hipStream_t st) {
-        if (bytes <= cap) return 0;
-        if (p) {
-            if (hipStreamSynchronize(st) != hipSuccess) return slm::fail(SLM_ERR_HIP, "hipStreamSynchronize failed");
-            (void)hipFree(p);
-        }
-        p = nullptr;
-        cap = 0;
-        RC(slm::dev_alloc(&p, bytes));
-        cap = bytes;
-        return 0;
-    }
-};
-
 }  // namespace
 
+using slm::DevBuf;
 using slm::fail;
 
 struct slm_spots {

@@ -165,6 +165,49 @@ def test_c64_tolerance_stop_and_intensity(gpu, c64_engine):
 
 
 @pytest.mark.gpu
+def test_c64_rebuilt_plan_matches_fresh_plan(gpu, c64_engine, monkeypatch):
+    """slm_plan_set_precision rebuilds an any-size engine for the other
+    precision inside the partials that plan creation sized for both. On the
+    smallest shape of the complex64 radix kernels (the shortest 2^k side they
+    are built on by the shortest panel length), 3 iterations from one warm-start phase: a plan taken F32 -> F64 ->
+    F32 gives bit for bit what a fresh plan gives, and at F64 what a plan
+    created under $SLM_PRECISION=f64 gives, each pair on the same geometry."""
+    h, w = 256, 600
+    t = _target((1, h, w), seed=21)
+    phi = np.random.default_rng(22).uniform(-np.pi, np.pi, (1, h, w)).astype(np.float32)
+
+    def plan():
+        return gpu.Plan(gpu.ALGO_GS, 1, h, w, gpu.TGT_F32, False, 3)
+
+    def run(p):
+        p.set_target(t)
+        p.set_phase(phi)
+        p.run(3)
+        phase, expected, stats, _ = p.read()
+        return p.generic_info(), phase, expected, stats
+
+    def assert_same(x, y):
+        assert x[0] == y[0]
+        for u, v in zip(x[1:], y[1:]):
+            assert u.tobytes() == v.tobytes()
+
+    with plan() as a:
+        assert a.engine() == ("radix-c64", "radix-c64")
+        a.set_precision(gpu.PRECISION_F64)
+        a64 = run(a)
+        a.set_precision(gpu.PRECISION_F32)
+        a32 = run(a)
+    with plan() as b:
+        b32 = run(b)
+    monkeypatch.setenv("SLM_PRECISION", "f64")
+    with plan() as c:
+        c64 = run(c)
+    assert a32[0]["engine"] == "radix-c64" and a64[0]["engine"] == "radix-c128"
+    assert_same(a32, b32)
+    assert_same(a64, c64)
+
+
+@pytest.mark.gpu
 def test_c64_incoming_amplitude(gpu, c64_engine):
     """An incoming intensity (src/algorithms.py:14-19) on a panel shape,
     warm-started as SURVEY.md 8c, against the faithful float64 oracle."""
