@@ -17,6 +17,9 @@
  *   slm_gsw / slm_plan_* with SLM_ALGO_GSW -> no reference counterpart: GS with Di Leonardo's
  *                                            per-pixel weight feedback, an addition next to
  *                                            the drop-in (see "weighted GS" below).
+ *   slm_plan_* with SLM_ALGO_MRAF         -> no reference counterpart: GS with a signal region
+ *                                            (mixed-region amplitude freedom) for extended,
+ *                                            flat shapes (see "MRAF" below).
  *   slm_spots_*                           -> no reference counterpart: weighted GS on a list
  *                                            of traps (fractional positions, defocus, any
  *                                            panel shape; see "trap lists" below).
@@ -34,6 +37,8 @@
 #ifndef SLM_HIP_H
 #define SLM_HIP_H
 
+#include <stdint.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -42,6 +47,8 @@ extern "C" {
 #define SLM_ALGO_GD 1
 /* weighted Gerchberg-Saxton (uniform trap intensities); no reference counterpart, see below */
 #define SLM_ALGO_GSW 2
+/* mixed-region amplitude freedom (smooth extended shapes); no reference counterpart, see below */
+#define SLM_ALGO_MRAF 3
 
 #define SLM_TGT_U8 0  /* uint8 target; amplitude = float16(sqrt(T)) as numpy does */
 #define SLM_TGT_F32 1 /* float32 target; amplitude = sqrtf(T) */
@@ -132,6 +139,39 @@ int slm_plan_set_lr(slm_plan* plan, const float* lr);             /* GD learning
 int slm_plan_set_feedback(slm_plan* plan, float feedback);
 int slm_plan_set_weights(slm_plan* plan, const float* weights);
 int slm_plan_read_weights(slm_plan* plan, float* weights);
+/* ---- MRAF (SLM_ALGO_MRAF): no reference counterpart -----------------------
+ * Mixed-region amplitude freedom (Pasienski and DeMarco 2008) for extended,
+ * flat targets, on which GS ends in speckle. Per hologram of S = h w pixels,
+ * with the signal region sr = R > 0, the mixing parameter 0 < m <= 1,
+ * P = S sum a_in^2 (= sum |fft2(B)|^2; S^2 for uniform light) and
+ * kappa = sqrt(P / sum_sr a_T^2) (float64, once per change of target, region
+ * or a_in: the target carries the whole power), every iteration does
+ *     B = a_in exp(i angle A);  C = fft2(B);  E = |C|^2
+ *     D = m kappa a_T C/|C| on sr (angle(0) = 0, as GS has it),  (1 - m) C off sr
+ *     A = ifft2(D)
+ * and starts exactly as GS does (ifft2(a_T) of the target as uploaded, or
+ * slm_plan_set_phase). T outside the region is ignored by the projection and
+ * by the statistics, which run over sr only:
+ *     error      = sum_sr (E max_sr(T) / max_sr(E) - T)^2 / N_sr
+ *     efficiency = sum_sr E / P
+ * stats rows hold max_sr E, sum_sr E^2, sum_sr E T and that error; tol stops on
+ * it. m = 1 with R all ones is GS, up to rounding. Plans of the fused engine
+ * only: other shapes and $SLM_ENGINE=float64 get SLM_ERR_UNSUPPORTED from
+ * slm_plan_create. There is no one-call or multi-GPU entry.
+ *
+ * slm_plan_set_region: R [batch][h][w] uint8, nonzero = signal. The plan keeps
+ *   it in a buffer of its own that runs read and never write. A hologram whose
+ *   region holds no pixel with T > 0 gives SLM_ERR_ARG (checked here against
+ *   the target set before, and again when a run is asked for). Running an MRAF
+ *   plan without a region gives SLM_ERR_STATE.
+ * slm_plan_set_mixing: m (default 0.4); values outside (0, 1] or non-finite
+ *   give SLM_ERR_ARG.
+ * slm_plan_read_efficiency: eff [batch][max_loops] of the last run; the rows of
+ *   a stopped hologram past its stop are left as the statistics rows are.
+ * All three give SLM_ERR_STATE on a plan of another algorithm.             */
+int slm_plan_set_region(slm_plan* plan, const uint8_t* region);
+int slm_plan_set_mixing(slm_plan* plan, float m);
+int slm_plan_read_efficiency(slm_plan* plan, double* eff);
 /* Enqueue one full run (setup + loops iterations + outputs) on the plan's
  * stream. tol as in `while error > tolerance`; checked != 0 evaluates that
  * test on the device after every iteration (required when tol > 0). */

@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("SLM_LIB_PATH") or os.path.join(os.path.dirname(os.pat
 ALGO_GS = 0
 ALGO_GD = 1
 ALGO_GSW = 2  # weighted GS: no reference counterpart (include/slm_hip.h)
+ALGO_MRAF = 3  # mixed-region amplitude freedom: no reference counterpart (include/slm_hip.h)
 TGT_U8 = 0
 TGT_F32 = 1
 PRECISION_F32 = 0
@@ -78,6 +79,9 @@ _SIGNATURES = [
     ("slm_plan_set_feedback", _c_int, [_vp, _c_float]),
     ("slm_plan_set_weights", _c_int, [_vp, _vp]),
     ("slm_plan_read_weights", _c_int, [_vp, _vp]),
+    ("slm_plan_set_region", _c_int, [_vp, _vp]),
+    ("slm_plan_set_mixing", _c_int, [_vp, _c_float]),
+    ("slm_plan_read_efficiency", _c_int, [_vp, _vp]),
     ("slm_plan_run", _c_int, [_vp, _c_int, _c_double, _c_int, _c_float]),
     ("slm_plan_run_timed", _c_int, [_vp, _c_int, _c_double, _c_int, _c_float, _vp, _vp]),
     ("slm_plan_sync", _c_int, [_vp]),
@@ -318,6 +322,22 @@ class Plan:
         (T > 0) and exactly 1 off it (slm_plan_read_weights)."""
         out = np.empty(self.shape, np.float32)
         check(self._lib.slm_plan_read_weights(self.handle, ptr(out)), "slm_plan_read_weights")
+        return out
+
+    def set_region(self, region: np.ndarray) -> None:
+        """MRAF: the signal region [batch][h][w], nonzero = signal (slm_plan_set_region)."""
+        a = np.ascontiguousarray(np.asarray(region) != 0, dtype=np.uint8).reshape(self.shape)
+        check(self._lib.slm_plan_set_region(self.handle, ptr(a)), "slm_plan_set_region")
+
+    def set_mixing(self, mixing: float) -> None:
+        """MRAF: the mixing parameter m in (0, 1] (slm_plan_set_mixing)."""
+        check(self._lib.slm_plan_set_mixing(self.handle, float(mixing)), "slm_plan_set_mixing")
+
+    def read_efficiency(self) -> np.ndarray:
+        """MRAF: sum_sr E / P per iteration of the last run, [batch][max_loops]
+        (slm_plan_read_efficiency)."""
+        out = np.empty((self.batch, self.max_loops), np.float64)
+        check(self._lib.slm_plan_read_efficiency(self.handle, ptr(out)), "slm_plan_read_efficiency")
         return out
 
     def run(self, loops: int, tol: float = 0.0, checked: bool = False, white_attention: float = 0.0) -> None:

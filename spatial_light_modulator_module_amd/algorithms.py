@@ -39,7 +39,9 @@ squares (the error's constant terms) kept exact in float64.
 Beyond the reference: ``weighted_gerchberg_saxton(demanded_output, args)`` and
 ``run_gsw`` run GS with a per-pixel weight feedback that evens out trap
 intensities ("Weighted GS"), on the fused kernels' shapes
-only. Nothing of the drop-in changes with it.
+only. Nothing of the drop-in changes with it. ``mraf(demanded_output, args)``
+and ``run_mraf`` run GS with a signal region (mixed-region amplitude freedom,
+for smooth extended shapes; DESIGN.md section 3, "MRAF"), on the same shapes.
 """
 from __future__ import annotations
 
@@ -51,7 +53,7 @@ import warnings
 import numpy as np
 
 from . import _lib
-from ._lib import ALGO_GD, ALGO_GS, ALGO_GSW, TGT_F32, TGT_U8
+from ._lib import ALGO_GD, ALGO_GS, ALGO_GSW, ALGO_MRAF, TGT_F32, TGT_U8
 
 # ---------------------------------------------------------------------------
 # input preparation (reference dtype rules)
@@ -288,6 +290,90 @@ def run_gsw(targets, loops, feedback=1.0, tol=0.0, ain=None, initial_phase=None,
     return out + (plan.read_weights(),) if return_weights else out
 
 
+MRAF_SHAPES = ("MRAF runs on the fused engine only: both sides of the target must be one of "
+               "64, 128, 256, 512, 1024, 2048, 4096 (powers of two) or 768, and $SLM_ENGINE=float64 must not be set")
+
+
+def signal_region(target, margin=8):
+    """The default MRAF signal region: the support T > 0 dilated by a square
+    of `margin` pixels each way, clipped at the edges (no wrap). uint8, 1 =
+    signal; the last two axes are the image."""
+    margin = int(margin)
+    if margin < 0:
+        raise ValueError(f"region margin must be >= 0, got {margin}")
+    sup = np.asarray(target) > 0
+    h, w = sup.shape[-2:]
+    rows = np.zeros_like(sup)
+    for d in range(-min(margin, h - 1), min(margin, h - 1) + 1):
+        rows[..., max(d, 0):h + min(d, 0), :] |= sup[..., max(-d, 0):h - max(d, 0), :]
+    out = np.zeros_like(sup)
+    for d in range(-min(margin, w - 1), min(margin, w - 1) + 1):
+        out[..., max(d, 0):w + min(d, 0)] |= rows[..., max(-d, 0):w - max(d, 0)]
+    return out.astype(np.uint8)
+
+
+def run_mraf(targets, regions, loops, mixing=0.4, tol=0.0, ain=None, initial_phase=None, return_efficiency=False):
+    """MRAF, mixed-region amplitude freedom (no reference counterpart;
+    include/slm_hip.h), on a batch [B][H][W]: GS whose amplitude constraint
+    m kappa a_T holds on the signal region `regions` != 0 only, (1 - m) C being
+    kept elsewhere. run_gs's return values, with the error, norm and max E
+    taken over the region; with return_efficiency the efficiency sum_sr E / P
+    per iteration (a list per hologram, as the errors) is appended. T outside
+    the region is ignored, except by the cold start, which is GS's own."""
+    t = np.asarray(targets)
+    tdev, tt = target_for_device(t)
+    if tdev.ndim != 3:
+        raise ValueError(f"targets must be [B][H][W], got shape {tdev.shape}")
+    b, h, w = tdev.shape
+    if (h not in _lib.SUPPORTED_LENGTHS or w not in _lib.SUPPORTED_LENGTHS
+            or os.environ.get("SLM_ENGINE") == "float64"):
+        raise ValueError(f"{MRAF_SHAPES} (got {h} x {w})")
+    mixing = float(mixing)
+    if not (np.isfinite(mixing) and 0 < mixing <= 1):
+        raise ValueError(f"mixing must be in (0, 1], got {mixing}")
+    r = np.asarray(regions)
+    if r.shape != tdev.shape:
+        raise ValueError(f"regions of shape {r.shape} do not match targets of shape {tdev.shape}")
+    sr = r != 0
+    for k in range(b):
+        if not np.any(sr[k] & (tdev[k] > 0)):
+            raise ValueError(f"the signal region of hologram {k} holds no pixel with T > 0")
+    if ain is not None and np.asarray(ain).shape != (h, w):
+        raise ValueError(f"ain of shape {np.asarray(ain).shape} does not match {(h, w)}")
+    if initial_phase is not None and np.asarray(initial_phase).shape != tdev.shape:
+        raise ValueError(f"initial_phase of shape {np.asarray(initial_phase).shape} does not match {tdev.shape}")
+    try:
+        plan = get_plan(ALGO_MRAF, b, h, w, tt, ain is not None, loops)
+    except _lib.SlmError as e:
+        if e.code == _lib.ERR_UNSUPPORTED:
+            raise ValueError(f"{MRAF_SHAPES} (got {h} x {w})") from e
+        raise
+    plan.set_target(tdev)
+    plan.set_region(sr)
+    if ain is not None:
+        plan.set_ain(ain)
+    plan.set_mixing(mixing)
+    plan.set_phase(initial_phase)
+    checked = tol > 0
+    plan.run(loops, tol, checked)
+    phase, e, stats, iters = plan.read()
+    if not checked:
+        if any(_stop_index(stats[k, :loops, 3], tol) not in (None, loops - 1) for k in range(b)):
+            plan.run(loops, tol, True)
+            phase, e, stats, iters = plan.read()
+            checked = True
+    errs, maxes, effs = [], [], []
+    eff = plan.read_efficiency()
+    for k in range(b):
+        n = loops if (not checked or iters[k] < 0) else int(iters[k])
+        errs.append([np.float64(v) for v in stats[k, :n, 3]])
+        maxes.append(stats[k, n - 1, 0])
+        effs.append([np.float64(v) for v in eff[k, :n]])
+    norm = np.array([np.float64(tdev[k][sr[k]].max()) for k in range(b)])
+    out = phase, e, errs, norm, np.array(maxes)
+    return out + (effs,) if return_efficiency else out
+
+
 def run_gs_multi(targets, loops, devices, tol=0.0, ain=None, feedback=None):
     """run_gs's contract over several GPUs from this one process
     (slm_gs_multi: contiguous shards, one host thread / plan per device).
@@ -467,7 +553,46 @@ def weighted_gerchberg_saxton(demanded_output, args):
     return hologram_from(phase[0]), expected_from(e[0], norm[0], emax[0]), error_evolution
 
 
-def _gerchberg_saxton_gif(t, args, ain, feedback=None):
+def mraf(demanded_output, args):
+    """MRAF (mixed-region amplitude freedom, Pasienski and DeMarco 2008) on the
+    GPU, for extended flat shapes, on which GS ends in speckle: the amplitude
+    is imposed on a signal region around the pattern only and left free
+    elsewhere. No reference counterpart; the return triple, the printed lines
+    and the exceptions are gerchberg_saxton's, with the error and the expected
+    outcome's scale taken over the region. Reads ``args.mixing`` (m, default
+    0.4), ``args.signal_region`` (an array, nonzero = signal, or None) and, with
+    None, ``args.region_margin`` (default 8): the region is then
+    signal_region(target, margin)."""
+    t = np.asarray(demanded_output)
+    _check_shape(t)
+    mixing = float(getattr(args, "mixing", 0.4))
+    region = getattr(args, "signal_region", None)
+    if region is None:
+        region = signal_region(t, getattr(args, "region_margin", 8))
+    region = np.asarray(region)
+    if region.shape != t.shape:
+        raise ValueError(f"signal region of shape {region.shape} does not match the target's {t.shape}")
+    ain = incoming_amplitude(args, t.shape)
+    tol = args.tolerance
+    if not _iterations_allowed(args):
+        print()
+        if args.print_info:
+            print()
+            printout(tol + 1, 0, [], args.plot_error)
+        raise UnboundLocalError("local variable 'expected_outcome' referenced before assignment")
+    if args.gif:
+        return _gerchberg_saxton_gif(t, args, ain, mraf=(region[None], mixing))
+    phase, e, errs, norm, emax = run_mraf(t[None], region[None], args.max_loops, mixing, tol, ain)
+    error_evolution = errs[0]
+    n = len(error_evolution)
+    _print_loops(n, args.max_loops)
+    if args.print_info:
+        print()
+        printout(error_evolution[-1], n, error_evolution, args.plot_error)
+    return hologram_from(phase[0]), expected_from(e[0], norm[0], emax[0]), error_evolution
+
+
+def _gerchberg_saxton_gif(t, args, ain, feedback=None, mraf=None):
     """GIF frames need intermediate states: run in warm-started chunks that end
     on every frame iteration (the GS state is angle(A) only; weighted GS, with
     a feedback exponent given, also hands its weights from chunk to chunk)."""
@@ -478,7 +603,9 @@ def _gerchberg_saxton_gif(t, args, ain, feedback=None):
     i = 0
     while i < loops:
         step = 1 if i % skip == 0 else min(skip - i % skip, loops - i)
-        if feedback is None:
+        if mraf is not None:  # the MRAF state is angle(A) only, as GS's
+            ph, e, errs, norm, emax = run_mraf(t[None], mraf[0], step, mraf[1], tol, ain, initial_phase=phase)
+        elif feedback is None:
             ph, e, errs, norm, emax = run_gs(t[None], step, tol, ain, initial_phase=phase)
         else:
             ph, e, errs, norm, emax, weights = run_gsw(t[None], step, feedback, tol, ain, initial_phase=phase,

@@ -138,6 +138,58 @@ __global__ void gsw_normalize_kernel(const TT* tgt, const float* g, float* out, 
     }
 }
 
+// MRAF, off the iteration path. Region constants of one hologram per workgroup,
+// in a fixed order (a rerun repeats bit for bit): over the signal region R > 0
+// the pixel count, sum a_T^2 (a_T as the iteration kernels form it), max T,
+// sum T^2 and the count of pixels with T > 0. tgt and region share one layout.
+template <int TT, typename TV>
+__global__ void __launch_bounds__(kGswThreads) mraf_region_kernel(const TV* tgt, const uint8_t* region, long long holo,
+                                                                   int B, double* rows) {
+    const int b = blockIdx.x;
+    const TV* t = tgt + (long long)b * holo;
+    const uint8_t* r = region + (long long)b * holo;
+    double mx = 0.0, n = 0.0, sa2 = 0.0, st2 = 0.0, np = 0.0, z0 = 0.0;
+    for (long long i = threadIdx.x; i < holo; i += kGswThreads) {
+        if (r[i] == 0) continue;
+        const float tf = (float)t[i];
+        const double a = (double)TgtLoad<TT>::amp(tf), td = (double)tf;
+        n += 1.0;
+        sa2 += a * a;
+        mx = fmax(mx, td);
+        st2 += td * td;
+        if (tf > 0.f) np += 1.0;
+    }
+    block_reduce_stats<kGswThreads>(mx, n, sa2);
+    lds_barrier();
+    block_reduce_stats<kGswThreads>(z0, st2, np);
+    if (threadIdx.x == 0) {
+        rows[MRAF_N * B + b] = n;
+        rows[MRAF_SUM_A2 * B + b] = sa2;
+        rows[MRAF_MAX_T * B + b] = mx;
+        rows[MRAF_SUM_T2 * B + b] = st2;
+        rows[MRAF_NPOS * B + b] = np;
+    }
+}
+// sum a_in^2 (one workgroup, fixed order)
+__global__ void __launch_bounds__(kGswThreads) mraf_ain_kernel(const float* ain, long long holo, double* out) {
+    double z0 = 0.0, s = 0.0, z1 = 0.0;
+    for (long long i = threadIdx.x; i < holo; i += kGswThreads) s += (double)ain[i] * (double)ain[i];
+    block_reduce_stats<kGswThreads>(z0, s, z1);
+    if (threadIdx.x == 0) *out = s;
+}
+// what follows from the reductions and m: 1 / N_sr, P = S sum a_in^2 (S^2 for
+// uniform light), and behind the region plane (kernels.hpp, mraf_scales) m kappa
+// with kappa = sqrt(P / sum_sr a_T^2), and 1 - m
+__global__ void mraf_scale_kernel(double* rows, double* scales, int B, double m, double holo, int has_ain) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double power = holo * (has_ain ? rows[kMrafRows * B] : holo);
+    rows[MRAF_INV_N * B + b] = 1.0 / rows[MRAF_N * B + b];
+    rows[MRAF_POWER * B + b] = power;
+    scales[b] = m * sqrt(power / rows[MRAF_SUM_A2 * B + b]);
+    scales[B + b] = 1.0 - m;
+}
+
 // plog: panel width log2 of the destination / source blocked layout
 // (layout_x_log2(lid): X buffers, the target; layout_y_log2(lid): Y, the GD field)
 // float / complex64 planes of 64-multiple sides move through LDS tiles
@@ -265,6 +317,13 @@ StatsParams stats_params(const PlanState& s, double tol) {
     p.tol = tol;
     p.max_loops = s.max_loops;
     p.nwg = s.nwg;
+    if (s.algo == SLM_ALGO_MRAF) {  // the error over the signal region, and the efficiency
+        p.norm = s.mraf + MRAF_MAX_T * s.B;
+        p.sum_t2 = s.mraf + MRAF_SUM_T2 * s.B;
+        p.inv_n = s.mraf + MRAF_INV_N * s.B;
+        p.power = s.mraf + MRAF_POWER * s.B;
+        p.eff = s.eff;
+    }
     return p;
 }
 
@@ -394,7 +453,6 @@ struct FusedEngine : Engine {
         ColParams c{};
         c.tgt = s.tgt;
         c.partials = s.partials;
-        c.e_out = s.e_out;
         c.stop_iter = s.stop;
         c.norm = s.normf;
         c.max_loops = s.max_loops;
@@ -466,7 +524,11 @@ struct FusedEngine : Engine {
         // weighted GS: the same iteration with COL_GSW_MAIN as its column pass.
         // Every run starts from the host-set weights (never written by a run) or ones.
         const bool gsw = s.algo == SLM_ALGO_GSW;
-        const int col_mode = gsw ? COL_GSW_MAIN : COL_GS_MAIN;
+        const bool mraf = s.algo == SLM_ALGO_MRAF;
+        const int col_mode = gsw ? COL_GSW_MAIN : mraf ? COL_MRAF_MAIN : COL_GS_MAIN;
+        if (mraf) {  // region and scales live in device memory: a captured run follows set_region / set_mixing
+            cp.region = s.region;
+        }
         if (gsw) {
             const long long n = (long long)s.B * s.holo;
             const int grid = (int)std::min<long long>(8192, (n + 255) / 256);
@@ -673,6 +735,45 @@ struct FusedEngine : Engine {
         return 0;
     }
 
+    // host uint8 [B][H][W] -> s.region (layout X, as a uint8 target)
+    int land_region(PlanState& s, const uint8_t* region) override {
+        const long long n = (long long)s.B * s.holo;
+        uint8_t* const stage = reinterpret_cast<uint8_t*>(y);  // scratch between runs
+        HIP_TRY(hipMemcpyAsync(stage, region, (size_t)n, hipMemcpyHostToDevice, s.stream));
+        return relayout(layout_x_log2(lid), (const uint8_t*)stage, s.region, n, s.H, s.W, true, s.stream);
+    }
+
+    int mraf_refresh(PlanState& s, bool reduce, int* bad_holo) override {
+        *bad_holo = -1;
+        if (reduce) {
+            if (s.tt == SLM_TGT_U8)
+                hipLaunchKernelGGL((mraf_region_kernel<TGT_U8, uint8_t>), dim3(s.B), dim3(kGswThreads), 0, s.stream,
+                                   (const uint8_t*)s.tgt, (const uint8_t*)s.region, s.holo, s.B, s.mraf);
+            else
+                hipLaunchKernelGGL((mraf_region_kernel<TGT_F32, float>), dim3(s.B), dim3(kGswThreads), 0, s.stream,
+                                   (const float*)s.tgt, (const uint8_t*)s.region, s.holo, s.B, s.mraf);
+            HIP_TRY(hipGetLastError());
+            if (s.has_ain) {
+                hipLaunchKernelGGL(mraf_ain_kernel, dim3(1), dim3(kGswThreads), 0, s.stream, (const float*)s.ain, s.holo,
+                                   s.mraf + (long long)kMrafRows * s.B);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        hipLaunchKernelGGL(mraf_scale_kernel, dim3((s.B + 255) / 256), dim3(256), 0, s.stream, s.mraf,
+                           const_cast<double*>(mraf_scales(s.region, s.B, s.holo)), s.B, (double)s.mixing, (double)s.holo, s.has_ain);
+        HIP_TRY(hipGetLastError());
+        if (reduce) {
+            std::vector<double> npos(s.B);
+            RC(copy_sync(npos.data(), s.mraf + MRAF_NPOS * s.B, (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost,
+                         s.stream));
+            for (int b = 0; b < s.B && *bad_holo < 0; ++b)
+                if (!(npos[b] > 0.0)) *bad_holo = b;
+        } else {
+            HIP_TRY(hipStreamSynchronize(s.stream));
+        }
+        return 0;
+    }
+
     // host float32 [B][H][W] -> s.weights0 (layout X); *bad: an entry on the
     // support is not positive and finite
     int land_weights(PlanState& s, const float* w, bool* bad) override {
@@ -782,8 +883,9 @@ struct FusedEngine : Engine {
         const long long ab = s.has_ain ? 4 : 0;
         const bool lin = s.algo == SLM_ALGO_GD && gd_mode == GD_LIN;  // + Y2 out (column) / in (row)
         switch (cls) {
-            case SLM_KERNEL_COL_MAIN:  // X (GD: F) in, T in, Y out (+ weighted GS: g in and out)
-                return px * (8 + tb + 8 + (lin ? 8 : 0) + (s.algo == SLM_ALGO_GSW ? 8 : 0));
+            case SLM_KERNEL_COL_MAIN:  // X (GD: F) in, T in, Y out (+ weighted GS: g in and out; MRAF: R in)
+                return px * (8 + tb + 8 + (lin ? 8 : 0) + (s.algo == SLM_ALGO_GSW ? 8 : 0) +
+                             (s.algo == SLM_ALGO_MRAF ? 1 : 0));
             case SLM_KERNEL_ROW_MAIN:                                 // Y in, X out (+ a_in) (+ field r/w for GD)
                 return px * (16 + ab + (s.algo == SLM_ALGO_GD ? 16 : 0) + (lin ? 8 : 0));
             case SLM_KERNEL_GD_STATS: return px * (8 + tb);           // X in, T in

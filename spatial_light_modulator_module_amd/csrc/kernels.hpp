@@ -16,6 +16,11 @@
 // projection epilogue updates g *= (a_T/|C|)^p on the support and projects with
 // a_T g, reading and writing g in place (+8 B per pixel on that pass).
 //
+// MRAF (COL_MRAF_MAIN; no reference counterpart) is the same iteration with
+// one uint8 region plane R in the target's layout: the projection epilogue
+// imposes m kappa a_T on the signal region R > 0 and keeps (1 - m) C off it,
+// and the statistics count region pixels only (+1 B per pixel on that pass).
+//
 // GD (src/algorithms.py:83-93) needs the global max of |F|^2 before the
 // gradient can be formed: its column side is one launch with a grid
 // max-barrier between the forward and the inverse transform where the grid is
@@ -71,8 +76,12 @@ struct ColParams {
     const float2* in_alt;    // GD ping-pong partner (expected-output kernel)
     float2* out;             // column-pass output Y
     const void* tgt;         // target intensity T [B][H][W] (uint8 or float)
-    double* partials;        // [B][max_loops][nwg] x 4 doubles: max, sum E^2, sum E T, 0 (COL_GSW_MAIN: sum g on the support)
-    float* e_out;            // |C|^2 of the final iteration [B][H][W]
+    double* partials;        // [B][max_loops][nwg] x 4 doubles: max, sum E^2, sum E T, 0 (COL_GSW_MAIN: sum g on the support; COL_MRAF_MAIN: sum E on the region)
+    // COL_MRAF_MAIN: signal region R [B][H][W], layout X (R > 0: signal), and behind
+    // the plane two rows of [B] doubles: m kappa, the amplitude scale on the region,
+    // and 1 - m, the factor of C off it (mraf_scales). In the slot of a pointer no
+    // kernel read, so the argument block of every other kernel is what it was.
+    const uint8_t* region;
     float* e_blk;            // COL_EXPECTED: |C|^2 in layout Y (relayout to e_out by the host)
     const int* stop_iter;    // [B]
     int checked;             // tolerance run: honour stop_iter (else it is never read)
@@ -125,7 +134,8 @@ enum ColMode : int {
     COL_GD_FUSED = 7,     // X -> fwd -> stats, grid barrier (global max) -> mask F (sP - T) -> inv -> Y
     COL_GD_LIN = 8,       // X -> fwd -> stats; mask F P -> inv -> Y, mask F T -> inv -> Y2 (no global max needed)
     COL_GSW_MAIN = 9,     // COL_GS_MAIN with the weighted-GS feedback: g *= (a_T/|C|)^p, D = a_T g C/|C|
-    COL_NUM_MODES = 10
+    COL_MRAF_MAIN = 10,   // COL_GS_MAIN with a signal region: D = m kappa a_T C/|C| on it, (1 - m) C off it
+    COL_NUM_MODES = 11
 };
 
 // target element types: 0 = uint8 (amplitude rounded to float16 as numpy's
@@ -402,6 +412,12 @@ __device__ __forceinline__ void store_coherent(double* dst, double v) {
 __device__ __forceinline__ double load_coherent(const double* src) {
     return __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const unsigned long long*>(src),
                                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+// MRAF: the scale rows behind the region plane (ColParams::region): [2][B]
+// doubles, m kappa then 1 - m (B holo bytes is a multiple of 8 for every radix-plan shape)
+__host__ __device__ __forceinline__ const double* mraf_scales(const uint8_t* region, int B, long long holo) {
+    return reinterpret_cast<const double*>(region + (long long)B * holo);
 }
 
 template <int P>
@@ -1088,7 +1104,8 @@ __global__ void __launch_bounds__((ColCfg<K, CW>::THREADS), 1) col_kernel(ColPar
     constexpr int SMEM = (ALT ? 2 : 1) * LINE * LW > CW * RS ? (ALT ? 2 : 1) * LINE * LW : CW * RS;
     __shared__ X smem[SMEM];
     constexpr bool kGsw = MODE == COL_GSW_MAIN;               // weighted GS: the GS pass plus the weight plane
-    constexpr bool kGs = MODE == COL_GS_MAIN || kGsw;         // the GS iteration pass
+    constexpr bool kMraf = MODE == COL_MRAF_MAIN;             // MRAF: the GS pass plus the region plane
+    constexpr bool kGs = MODE == COL_GS_MAIN || kGsw || kMraf;  // the GS iteration pass
 
     // a thread carries columns c .. c + L - 1 of the tile (adjacent in the
     // blocked layout: one 16-B access for L = 2)
@@ -1203,6 +1220,16 @@ __global__ void __launch_bounds__((ColCfg<K, CW>::THREADS), 1) col_kernel(ColPar
             // the target is consumed in the middle of the transforms: fetch it with the field
 #pragma unroll
             for (int m = 0; m < E; ++m) ld_tgt(base + m * kStep, tv, m);
+        }
+        if constexpr (kMraf) {
+            // the region sits where the target does (layout X) and is loaded as a uint8
+            // target is. Off the region T plays no part (projection and statistics
+            // ignore it), so the flag travels in the target's own register: -1 there.
+#pragma unroll
+            for (int m = 0; m < E; ++m)
+#pragma unroll
+                for (int l = 0; l < L; ++l)
+                    if (p.region[base + m * kStep + l] == 0) tv[l][m] = -1.f;
         }
         if constexpr (kGsw) {  // the weights sit where the target does (layout X)
 #pragma unroll
@@ -1401,10 +1428,32 @@ __global__ void __launch_bounds__((ColCfg<K, CW>::THREADS), 1) col_kernel(ColPar
             // partials and T = a_T^2 show at 1e-4 .. 1e-3 of such an error. p = 0 is
             // GS by definition and reports GS's own sums, bit for bit.
             double s2d = 0.0, std_ = 0.0;
+            // COL_MRAF_MAIN: the same float64 sums over the region only (the region
+            // error cancels the same way), and sum E over it for the efficiency
+            double sed = 0.0;
+            S mraf_on = 0, mraf_off = 0;
+            if constexpr (kMraf) {
+                const double* k = mraf_scales(p.region, p.B, p.holo);
+                mraf_on = (S)k[b];
+                mraf_off = (S)k[p.B + b];
+            }
             auto epi = [&](int l, int m, C& z) {
                 const S e = z.x * z.x + z.y * z.y;
                 const float tl = tv[l][m];
-                if constexpr (kGs) {
+                if constexpr (kMraf) {
+                    const bool on = tl >= 0.f;  // the signal region (load: -1 off it)
+                    const float ef = (float)e;
+                    const float tr = on ? tl : 0.f;
+                    const double ed = on ? (double)ef : 0.0;
+                    mxf = fmaxf(mxf, on ? ef : 0.f);
+                    s2d = fma(ed, ed, s2d);
+                    std_ = fma(ed, (double)tr, std_);
+                    sed += ed;
+                    if (e_blk) e_blk[eb + m * kStepY + l] = ef;
+                    // D = m kappa a_T C/|C| on the region, (1 - m) C off it
+                    const C zr = unit_scale(z, mraf_on * (S)TgtLoad<TT>::amp(tr));
+                    z = on ? zr : mk<C>(z.x * mraf_off, z.y * mraf_off);
+                } else if constexpr (kGs) {
                     const float ef = (float)e;  // |C|^2 as the reference's float64 expected_outcome sees it
                     mxf = fmaxf(mxf, ef);
                     s2f = fmaf(ef * stat_k, ef, s2f);
@@ -1500,12 +1549,22 @@ __global__ void __launch_bounds__((ColCfg<K, CW>::THREADS), 1) col_kernel(ColPar
                     st = std_;
                 }
             }
+            if constexpr (kMraf) {
+                s2 = s2d;
+                st = std_;
+            }
             if constexpr (kGs || MODE == COL_GD_STATS) {
                 double gsd = 0.0;
                 if constexpr (kGsw) {  // sum g over the tile's support: a fold of its own, ahead of the statistics'
                     double gs = (double)gsf, z0 = 0.0, z1 = 0.0;
                     block_reduce_stats<THREADS>(z0, gs, z1);
                     gsd = gs;
+                    lds_barrier();
+                }
+                if constexpr (kMraf) {  // sum E over the tile's region pixels
+                    double z0 = 0.0, z1 = 0.0;
+                    block_reduce_stats<THREADS>(z0, sed, z1);
+                    gsd = sed;
                     lds_barrier();
                 }
                 block_reduce_stats<THREADS>(mx, s2, st);
@@ -1535,6 +1594,11 @@ struct StatsParams {
     const double* norm;      // [B] max(T)
     const double* sum_t2;    // [B] sum T^2
     double inv_s;            // 1 / S
+    // MRAF: norm and sum_t2 are the region's; 1 / N_sr per hologram in place of
+    // inv_s, and the efficiency sum E (region) / P per (hologram, iteration)
+    const double* inv_n;     // [B], nullptr: inv_s
+    const double* power;     // [B] P = S sum a_in^2
+    double* eff;             // [B][max_loops], nullptr: none
     double tol;
     int max_loops;
     int nwg;
@@ -1551,13 +1615,20 @@ __device__ __forceinline__ void reduce_slab(const StatsParams& p, int b, int i, 
         st += part[k * 4 + 2];
     }
     block_reduce_stats<256>(mx, s2, st);
+    if (p.eff) {  // uniform
+        double se = 0.0, z0 = 0.0, z1 = 0.0;
+        for (int k = threadIdx.x; k < p.nwg; k += 256) se += part[k * 4 + 3];
+        lds_barrier();
+        block_reduce_stats<256>(z0, se, z1);
+        if (threadIdx.x == 0) p.eff[(long long)b * p.max_loops + i] = __ddiv_rn(se, p.power[b]);
+    }
     if (threadIdx.x == 0) {
         // error_f (src/algorithms.py:161-162) of E * norm / max(E) against T,
         // expanded so that E never has to be stored: (s^2 SE2 - 2 s SET + ST2) / S.
         const double s = __ddiv_rn(p.norm[b], mx);
         double a = __dmul_rn(__dmul_rn(s, s), s2);
         double c = __dmul_rn(__dmul_rn(2.0, s), st);
-        const double err = __dmul_rn(__dadd_rn(__dsub_rn(a, c), p.sum_t2[b]), p.inv_s);
+        const double err = __dmul_rn(__dadd_rn(__dsub_rn(a, c), p.sum_t2[b]), p.inv_n ? p.inv_n[b] : p.inv_s);
         out4[0] = mx;
         out4[1] = s2;
         out4[2] = st;

@@ -43,6 +43,9 @@ ColFn col_table_cw(int mode, int tt) {
             case COL_GSW_MAIN:  // weighted GS: wherever COL_GS_MAIN is built; a float32 target stays T (exact statistics)
                 return u8 ? col_kernel<N, CW, COL_GSW_MAIN, TGT_U8, P, LID>
                           : tt == TGT_F32 ? col_kernel<N, CW, COL_GSW_MAIN, TGT_F32, P, LID> : nullptr;
+            case COL_MRAF_MAIN:  // MRAF: wherever COL_GS_MAIN is built; a float32 target stays T, as for weighted GS
+                return u8 ? col_kernel<N, CW, COL_MRAF_MAIN, TGT_U8, P, LID>
+                          : tt == TGT_F32 ? col_kernel<N, CW, COL_MRAF_MAIN, TGT_F32, P, LID> : nullptr;
             case COL_REAL_INV:
                 return u8 ? col_kernel<N, CW, COL_REAL_INV, TGT_U8, P, LID>
                           : tt == TGT_AMP ? col_kernel<N, CW, COL_REAL_INV, TGT_AMP, P, LID>

@@ -52,6 +52,15 @@ struct PlanState {
     float* weights0 = nullptr;    // weighted GS: host-set initial weights, never overwritten by a run
     bool weights_set = false;     // ... in force (else every run starts from ones)
     float feedback = 1.f;         // weighted GS: exponent p of g *= (a_T / |C|)^p
+    // MRAF: signal region R (R > 0), laid out like a uint8 target, and its two scale
+    // rows behind it (kernels.hpp, mraf_scales); runs never write either
+    uint8_t* region = nullptr;
+    float mixing = 0.4f;          // MRAF: mixing parameter m
+    // MRAF: per-hologram constants, kMrafRows rows of [B] doubles (MrafRow), then
+    // sum a_in^2; reduced on the device when the target, the region or a_in
+    // changes, rescaled when m does (FusedEngine::mraf_refresh)
+    double* mraf = nullptr;
+    double* eff = nullptr;        // MRAF: efficiency sum_sr E / P, [B][max_loops]
     float* lr = nullptr;          // GD learning rate per iteration
     float* phase_out = nullptr;
     float* e_out = nullptr;       // |C|^2 (GS) / |F|^2 (GD) of the last iteration, float32
@@ -67,8 +76,16 @@ struct PlanState {
     EventPool* timing = nullptr;  // a timed run is being enqueued: every launch takes an event pair
 };
 
-// GS and weighted GS share the iteration, the warm start and the float32-target amplitude plane
-inline bool gs_like(int algo) { return algo == SLM_ALGO_GS || algo == SLM_ALGO_GSW; }
+// GS, weighted GS and MRAF share the iteration and the warm start
+inline bool gs_like(int algo) { return algo == SLM_ALGO_GS || algo == SLM_ALGO_GSW || algo == SLM_ALGO_MRAF; }
+
+// rows of PlanState::mraf, each [B]: the reductions over the signal region sr
+// (pixels, sum a_T^2, max T, sum T^2, pixels with T > 0) and what follows from
+// them (1 / N_sr, P = S sum a_in^2); m kappa and 1 - m sit behind the region
+// plane, where the column kernel reads them (kernels.hpp, mraf_scales)
+enum MrafRow : int {
+    MRAF_N = 0, MRAF_SUM_A2, MRAF_MAX_T, MRAF_SUM_T2, MRAF_NPOS, MRAF_INV_N, MRAF_POWER, kMrafRows
+};
 
 struct Engine {
     virtual ~Engine() {}
@@ -82,6 +99,12 @@ struct Engine {
     // validated on the support; the weights to the host (mean 1 on the support)
     virtual int land_weights(PlanState& s, const float* w, bool* bad);
     virtual int read_weights(PlanState& s, bool fresh, float* w);
+    // MRAF (the fused engine only): host uint8 [B][H][W] -> s.region; the region
+    // constants of s.mraf from the target, the region, a_in and m (`reduce`: the
+    // reductions too, else the two rows that depend on m alone); *bad_holo: the
+    // first hologram whose region holds no pixel with T > 0, or -1
+    virtual int land_region(PlanState& s, const uint8_t* region);
+    virtual int mraf_refresh(PlanState& s, bool reduce, int* bad_holo);
     // one full run (setup, loops iterations, phase and expected output), on s.stream
     virtual int enqueue(PlanState& s, int loops, double tol, int checked, float wa, bool phase_set,
                         bool field_set) = 0;
@@ -166,6 +189,8 @@ struct slm_plan {
     bool ran = false;          // a run was enqueued (the state buffers hold something)
     bool field_fresh = false;  // set_field since the last run: the plan's field is field0
     bool weights_fresh = false;  // set_weights since the last run: the plan's weights are weights0 (or ones)
+    bool region_set = false;     // MRAF: slm_plan_set_region succeeded
+    int mraf_bad = -1;           // MRAF: a hologram whose region holds no pixel with T > 0 (a run refuses it)
     // parameters of the last enqueued run (settling a faulted run redoes it)
     int last_loops = 0, last_checked = 0;
     double last_tol = 0.0;

@@ -78,6 +78,12 @@ int Engine::land_weights(PlanState&, const float*, bool*) {
 int Engine::read_weights(PlanState&, bool, float*) {
     return fail(SLM_ERR_STATE, "weights belong to weighted-GS plans of the fused engine");
 }
+int Engine::land_region(PlanState&, const uint8_t*) {
+    return fail(SLM_ERR_STATE, "a signal region belongs to MRAF plans of the fused engine");
+}
+int Engine::mraf_refresh(PlanState&, bool, int*) {
+    return fail(SLM_ERR_STATE, "a signal region belongs to MRAF plans of the fused engine");
+}
 int Engine::read_trace(PlanState&, int, unsigned long long*) {
     return fail(SLM_ERR_STATE, "no trace buffer (set SLM_TRACE_BUF=1 before creating the plan)");
 }
@@ -200,12 +206,37 @@ int drop_graph(slm_plan* p) {
     return 0;
 }
 
+int mraf_no_support(int b) {
+    return fail(SLM_ERR_ARG, "the signal region of hologram %d holds no pixel with T > 0", b);
+}
+
+// MRAF runs need a region in force, with target light inside it (a replayed run is checked too)
+int mraf_ready(const slm_plan* p) {
+    if (p->s.algo != SLM_ALGO_MRAF) return 0;
+    if (!p->region_set) return fail(SLM_ERR_STATE, "signal region not set (slm_plan_set_region)");
+    if (p->target_set && p->mraf_bad >= 0) return mraf_no_support(p->mraf_bad);
+    return 0;
+}
+
+// MRAF: the region constants follow every change of target, region, a_in or m
+// (reduce = false: m alone changed)
+int mraf_update(slm_plan* p, bool reduce) {
+    if (p->s.algo != SLM_ALGO_MRAF || !p->target_set || !p->region_set) return 0;
+    Engine* e = nullptr;
+    RC(engine_of(p, &e));
+    int bad = -1;
+    RC(e->mraf_refresh(p->s, reduce, &bad));
+    if (reduce) p->mraf_bad = bad;
+    return 0;
+}
+
 int enqueue_run(slm_plan* p, int loops, double tol, int checked, float wa) {
     if (!p) return fail(SLM_ERR_ARG, "null plan");
     if (!p->target_set) return fail(SLM_ERR_STATE, "target not set");
     if (loops < 1 || loops > p->s.max_loops)
         return fail(SLM_ERR_ARG, "loops %d outside [1, %d]", loops, p->s.max_loops);
     if (p->s.algo == SLM_ALGO_GD && !p->lr_set) return fail(SLM_ERR_STATE, "learning rates not set");
+    RC(mraf_ready(p));
     Engine* e = nullptr;
     RC(engine_of(p, &e));
     HIP_TRY(hipSetDevice(p->s.device));
@@ -237,7 +268,8 @@ void free_plan(slm_plan* p) {
     gather_free(p->gather);
     for (void* ptr : {(void*)s.xa, s.tgt, (void*)s.ain, (void*)s.phase_in, (void*)s.phase_out, (void*)s.e_out,
                       (void*)s.partials, (void*)s.stats, (void*)s.stop, (void*)s.norm, (void*)s.normf,
-                      (void*)s.sum_t2, (void*)s.field0, (void*)s.lr, (void*)p->ts_part, (void*)s.weights0})
+                      (void*)s.sum_t2, (void*)s.field0, (void*)s.lr, (void*)p->ts_part, (void*)s.weights0,
+                      (void*)s.region, (void*)s.mraf, (void*)s.eff})
         if (ptr) (void)hipFree(ptr);
     for (auto& e : p->events.pool) {
         (void)hipEventDestroy(e.first);
@@ -255,7 +287,7 @@ int plan_create_on(int device, int algo, int batch, int height, int width, int t
                    int max_loops, slm_plan** out) {
     if (!out) return fail(SLM_ERR_ARG, "null output pointer");
     *out = nullptr;
-    if (algo != SLM_ALGO_GS && algo != SLM_ALGO_GD && algo != SLM_ALGO_GSW)
+    if (algo != SLM_ALGO_GS && algo != SLM_ALGO_GD && algo != SLM_ALGO_GSW && algo != SLM_ALGO_MRAF)
         return fail(SLM_ERR_ARG, "unknown algorithm %d", algo);
     if (batch < 1 || max_loops < 1) return fail(SLM_ERR_ARG, "batch and max_loops must be >= 1");
     if (tgt_type != SLM_TGT_U8 && tgt_type != SLM_TGT_F32) return fail(SLM_ERR_ARG, "unknown target type");
@@ -279,6 +311,12 @@ int plan_create_on(int device, int algo, int batch, int height, int width, int t
     if (algo == SLM_ALGO_GSW && p->any_size)
         return fail(SLM_ERR_UNSUPPORTED,
                     "weighted GS (SLM_ALGO_GSW) runs on the fused engine only: both sides must be one of 64, 128, "
+                    "256, 512, 1024, 2048, 4096 (powers of two) or 768%s; got %d x %d",
+                    forced64 ? ", and SLM_ENGINE=float64 must not be set" : "", height, width);
+    // ... and so is MRAF
+    if (algo == SLM_ALGO_MRAF && p->any_size)
+        return fail(SLM_ERR_UNSUPPORTED,
+                    "MRAF (SLM_ALGO_MRAF) runs on the fused engine only: both sides must be one of 64, 128, "
                     "256, 512, 1024, 2048, 4096 (powers of two) or 768%s; got %d x %d",
                     forced64 ? ", and SLM_ENGINE=float64 must not be set" : "", height, width);
     s.algo = algo;
@@ -325,6 +363,11 @@ int plan_create_on(int device, int algo, int batch, int height, int width, int t
         RC(dev_alloc(&s.lr, (size_t)max_loops * sizeof(float)));
     }
     if (algo == SLM_ALGO_GSW) RC(dev_alloc(&s.weights0, n * sizeof(float)));
+    if (algo == SLM_ALGO_MRAF) {
+        RC(dev_alloc(&s.region, n + (size_t)2 * batch * sizeof(double)));  // the plane, then the scale rows
+        RC(dev_alloc(&s.mraf, ((size_t)kMrafRows * batch + 1) * sizeof(double)));
+        RC(dev_alloc(&s.eff, (size_t)batch * max_loops * sizeof(double)));
+    }
     RC(dev_alloc(&s.tgt, n * (tgt_type == SLM_TGT_U8 ? 1 : 4)));
     if (has_ain) RC(dev_alloc(&s.ain, (size_t)s.holo * sizeof(float)));
     RC(dev_alloc(&s.phase_out, n * sizeof(float)));
@@ -535,7 +578,8 @@ int slm_plan_set_target(slm_plan* p, const void* tgt) {
     // host-set weights were validated on the previous target's support
     s.weights_set = false;
     p->weights_fresh = false;
-    return 0;
+    // MRAF: a region that no longer fits the target is refused when a run is asked for
+    return mraf_update(p, true);
 }
 
 int slm_plan_set_precision(slm_plan* p, int precision) {
@@ -583,7 +627,7 @@ int slm_plan_set_ain(slm_plan* p, const float* ain) {
     // before its DMA has landed.
     HIP_TRY(hipMemcpyAsync(p->s.ain, ain, (size_t)p->s.holo * sizeof(float), hipMemcpyHostToDevice, p->s.stream));
     HIP_TRY(hipStreamSynchronize(p->s.stream));
-    return 0;
+    return mraf_update(p, true);
 }
 
 int slm_plan_set_phase(slm_plan* p, const float* phase) {
@@ -668,6 +712,45 @@ int slm_plan_read_weights(slm_plan* p, float* w) {
     return e->read_weights(s, fresh, w);
 }
 
+int slm_plan_set_region(slm_plan* p, const uint8_t* region) {
+    if (!p) return fail(SLM_ERR_ARG, "null plan");
+    PlanState& s = p->s;
+    if (s.algo != SLM_ALGO_MRAF) return fail(SLM_ERR_STATE, "a signal region applies to MRAF plans");
+    if (!region) return fail(SLM_ERR_ARG, "null region");
+    Engine* e = nullptr;
+    RC(engine_of(p, &e));
+    HIP_TRY(hipSetDevice(s.device));
+    HIP_TRY(hipStreamSynchronize(s.stream));  // the staging buffer is scratch of a queued run
+    p->region_set = false;
+    p->mraf_bad = -1;
+    RC(e->land_region(s, region));
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    p->region_set = true;
+    RC(mraf_update(p, true));
+    if (p->mraf_bad >= 0) {
+        p->region_set = false;
+        return mraf_no_support(p->mraf_bad);
+    }
+    return 0;
+}
+
+int slm_plan_set_mixing(slm_plan* p, float m) {
+    if (!p) return fail(SLM_ERR_ARG, "null plan");
+    if (!(m > 0.f && m <= 1.f)) return fail(SLM_ERR_ARG, "mixing parameter %g is not in (0, 1]", (double)m);
+    if (p->s.algo != SLM_ALGO_MRAF) return fail(SLM_ERR_STATE, "the mixing parameter applies to MRAF plans");
+    HIP_TRY(hipSetDevice(p->s.device));
+    p->s.mixing = m;
+    return mraf_update(p, false);
+}
+
+int slm_plan_read_efficiency(slm_plan* p, double* eff) {
+    if (!p || !eff) return fail(SLM_ERR_ARG, "null argument");
+    PlanState& s = p->s;
+    if (s.algo != SLM_ALGO_MRAF) return fail(SLM_ERR_STATE, "the efficiency is a statistic of MRAF plans");
+    RC(slm_plan_sync(p));
+    return copy_sync(eff, s.eff, (size_t)s.B * s.max_loops * sizeof(double), hipMemcpyDeviceToHost, s.stream);
+}
+
 int slm_plan_set_lr(slm_plan* p, const float* lr) {
     if (!p || !lr) return fail(SLM_ERR_ARG, "null argument");
     PlanState& s = p->s;
@@ -683,6 +766,7 @@ int slm_plan_run(slm_plan* p, int loops, double tol, int checked, float wa) {
     Engine* e = nullptr;
     RC(engine_of(p, &e));
     PlanState& s = p->s;
+    RC(mraf_ready(p));
     p->field_fresh = false;  // replays skip enqueue_run
     p->weights_fresh = false;
     p->last_loops = loops;

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from . import constants as c
-from .algorithms import gerchberg_saxton, gradient_descent, weighted_gerchberg_saxton
+from .algorithms import gerchberg_saxton, gradient_descent, mraf, weighted_gerchberg_saxton
 
 
 def main(args):
@@ -83,13 +83,15 @@ def quarter(image):
     return ground
 
 
-def prepare_target(img_name, args):
-    """uint8 (768, 1024) target (src/generate_hologram.py:102-110)."""
+def prepare_target(img_name, args, invert=None):
+    """uint8 (768, 1024) target (src/generate_hologram.py:102-110). invert
+    overrides args.invert (the MRAF region image takes the target's geometric
+    steps but is never inverted)."""
     import PIL.ImageOps
     from PIL import Image
 
     target_img = Image.open(f"images/{img_name}").convert("L")
-    if args.invert:
+    if args.invert if invert is None else invert:
         target_img = PIL.ImageOps.invert(target_img)
     target_img = pad_to_square(target_img)
     if args.quarterize:
@@ -100,8 +102,12 @@ def prepare_target(img_name, args):
 def make_hologram(args):
     """src/generate_hologram.py:70-79."""
     algorithm = {"gerchberg_saxton": gerchberg_saxton,
-                 "weighted_gerchberg_saxton": weighted_gerchberg_saxton}.get(args.algorithm, gradient_descent)
+                 "weighted_gerchberg_saxton": weighted_gerchberg_saxton,
+                 "mraf": mraf}.get(args.algorithm, gradient_descent)
     target = prepare_target(args.img_name, args)
+    if args.algorithm == "mraf":  # nonzero = signal; without --region the margin rule of algorithms.mraf
+        region = getattr(args, "region", None)
+        args.signal_region = None if region is None else prepare_target(region, args, invert=False)
     if args.gif:
         add_gif_dirs(args)
         remove_files_in_dir(args.gif_source_dir)
@@ -254,10 +260,18 @@ def build_parser():
     p.add_argument("-q", "--quarterize", action="store_true", help="paste the image into one quadrant")
     p.add_argument("-i", "--invert", action="store_true", help="invert colors of the target image")
     p.add_argument("-alg", "--algorithm", default="gerchberg_saxton",
-                   choices=["gerchberg_saxton", "gradient_descent", "weighted_gerchberg_saxton"],
-                   help="algorithm (weighted_gerchberg_saxton: GS with trap-intensity feedback)")
+                   choices=["gerchberg_saxton", "gradient_descent", "weighted_gerchberg_saxton", "mraf"],
+                   help="algorithm (weighted_gerchberg_saxton: GS with trap-intensity feedback; "
+                        "mraf: GS with a signal region, for smooth extended shapes)")
     p.add_argument("--feedback", default=1.0, type=float, metavar="FLOAT",
                    help="weight feedback exponent of weighted_gerchberg_saxton")
+    p.add_argument("--mixing", default=0.4, type=float, metavar="FLOAT",
+                   help="mixing parameter m in (0, 1] of mraf")
+    p.add_argument("--region", default=None, type=str, metavar="IMAGE",
+                   help="signal region of mraf: an image from the images directory, nonzero = signal "
+                        "(default: the target's support grown by --region_margin)")
+    p.add_argument("--region_margin", default=8, type=int, metavar="INT",
+                   help="pixels by which mraf grows the target's support into its signal region")
     p.add_argument("-tol", "--tolerance", default=0, metavar="FLOAT", type=float,
                    help="algorithm stops when error descends under tolerance")
     p.add_argument("-l", "--max_loops", default=42, metavar="INTEGER", type=int,
