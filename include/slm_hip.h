@@ -206,6 +206,59 @@ int slm_plan_set_target_stats(slm_plan* plan, const double* norm, const double* 
  * the field a chunked run continues from with slm_plan_set_field (GIF frames,
  * src/algorithms.py:94-101). */
 int slm_plan_read_field(slm_plan* plan, float* field);
+/* Image sequences: F frames of targets (moving traps drawn as pictures) as one
+ * chain enqueued on the plan's stream, on GS, weighted-GS and MRAF plans of any
+ * engine the algorithm runs on. The chain is, bit for bit, this host loop:
+ *     for f = 0 .. F-1:
+ *         slm_plan_set_target(targets[f])      (MRAF with regions: and
+ *                                               slm_plan_set_region(regions[f]))
+ *         f > 0: slm_plan_set_phase(the float32 phase frame f-1 ended with)
+ *         f = 0: the start the plan has (slm_plan_set_phase, or the cold start)
+ *         slm_plan_run(f = 0 ? loops_first : loops, tol, tol > 0, 0)
+ *         outputs of frame f: phase, E, the statistics rows, iters, the
+ *         efficiency rows (MRAF), and frame = the SLM_QUANT_* `rule` of
+ *         slm_quantize applied to ((double)phase, mask, ct2pi)
+ * without the host in it: the frames are uploaded once, each is landed from
+ * device memory by the kernels slm_plan_set_target runs, the phase passes from
+ * frame to frame on the device, and one epilogue kernel per frame writes the
+ * uint8 frame, the next start and the kept phase. Nothing synchronises with the
+ * host between frames. Weighted-GS weights return to ones at every frame, as
+ * slm_plan_set_target has it.
+ * slm_plan_sequence: targets [n_frames][batch][h][w] of the plan's target type;
+ *   regions [n_frames][batch][h][w] uint8 (MRAF plans only) or NULL = the region
+ *   in force serves every frame; mask [h][w] float64 or NULL, ct2pi and rule as
+ *   slm_quantize; want_frames / want_phases / want_expected != 0 keep the uint8
+ *   frames / the float32 phases / E of every frame on the device for
+ *   slm_plan_sequence_read. With resume != 0, frame 0 of the call is treated as
+ *   a frame f > 0 of the previous sequence on this plan (starts from its last
+ *   phase, runs `loops`): a sequence cut in two is the uncut one. Everything is
+ *   checked on the host before anything is enqueued. SLM_ERR_ARG: n_frames < 1,
+ *   loops_first or loops outside 1 .. max_loops, tol negative or not finite, an
+ *   unknown rule, ct2pi not positive and finite, an MRAF frame whose region
+ *   holds no pixel with T > 0 (the message names frame and hologram; checked on
+ *   the host over all frames, so the chain's refresh needs no copy back).
+ *   SLM_ERR_STATE: a GD plan, has_ain without slm_plan_set_ain, regions on a
+ *   plan that is not MRAF, MRAF with neither regions nor a region in force,
+ *   resume without a previous sequence or after any slm_plan_set_* or
+ *   slm_plan_run since. SLM_ERR_HIP when a sequence buffer cannot be allocated
+ *   (they are sized at the call, only grow and go with the plan; the plan stays
+ *   usable). After a sequence the plan is as after slm_plan_set_target (and
+ *   slm_plan_set_region) with the last frame: a start phase the caller set
+ *   before is still in force, a captured run stays valid, and slm_plan_read
+ *   gives SLM_ERR_STATE until the next slm_plan_run.
+ * slm_plan_sequence_read: waits for the chain, then copies what is asked for
+ *   (any pointer NULL): frames [n_frames][batch][h][w] uint8, phases and
+ *   expected [n_frames][batch][h][w] float32, stats [n_frames][batch][rows][4]
+ *   and efficiency [n_frames][batch][rows] (MRAF) with rows = max(loops_first,
+ *   loops), iters [n_frames][batch] as slm_plan_read has them. Rows a frame did
+ *   not reach are as slm_plan_read would leave them. SLM_ERR_STATE before a
+ *   sequence, for an output the sequence was not asked to keep, and for the
+ *   efficiency of a plan that is not MRAF.                                    */
+int slm_plan_sequence(slm_plan* plan, int n_frames, const void* targets, const uint8_t* regions, int loops_first,
+                      int loops, double tol, int resume, const double* mask, double ct2pi, int rule, int want_frames,
+                      int want_phases, int want_expected);
+int slm_plan_sequence_read(slm_plan* plan, unsigned char* frames, float* phases, float* expected, double* stats,
+                           double* efficiency, int* iters);
 /* algorithmic HBM bytes moved by one launch of a kernel class */
 long long slm_plan_kernel_bytes(slm_plan* plan, int kernel_class);
 /* info[0] = column tile width, info[1] = column workgroups per hologram,

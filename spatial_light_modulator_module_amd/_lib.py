@@ -92,6 +92,9 @@ _SIGNATURES = [
     ("slm_plan_read_target_stats", _c_int, [_vp, _vp, _vp]),
     ("slm_plan_set_target_stats", _c_int, [_vp, _vp, _vp]),
     ("slm_plan_read_field", _c_int, [_vp, _vp]),
+    ("slm_plan_sequence", _c_int, [_vp, _c_int, _vp, _vp, _c_int, _c_int, _c_double, _c_int, _vp, _c_double, _c_int,
+                                   _c_int, _c_int, _c_int]),
+    ("slm_plan_sequence_read", _c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("slm_plan_kernel_bytes", ctypes.c_longlong, [_vp, _c_int]),
     ("slm_plan_info", _c_int, [_vp, _vp]),
     ("slm_plan_generic_info", _c_int, [_vp, _vp]),
@@ -378,6 +381,54 @@ class Plan:
         check(self._lib.slm_plan_read(self.handle, ptr(out_phase), ptr(out_exp), ptr(out_stats), ptr(out_iters)),
               "slm_plan_read")
         return out_phase, out_exp, out_stats, out_iters
+
+    def sequence(self, targets, regions=None, loops_first: int = 5, loops: int = 5, tol: float = 0.0,
+                 resume: bool = False, mask=None, ct2pi=256.0, rule: int = QUANT_PIL, frames: bool = True,
+                 phases: bool = False, expected: bool = False) -> None:
+        """slm_plan_sequence: targets [F][batch][h][w] (and, for MRAF plans,
+        regions of the same shape, or None for the region in force) as one
+        enqueued chain, bit for bit the loop of set_target / set_phase(previous
+        phase) / run(loops_first for frame 0, else loops; tol; checked = tol > 0)
+        / quantize per frame. Returns once the chain is enqueued; sequence_read
+        waits."""
+        dt = np.uint8 if self.tgt_type == TGT_U8 else np.float32
+        t = np.ascontiguousarray(targets, dtype=dt)
+        per = self.batch * self.height * self.width
+        if t.ndim < 3 or t.size == 0 or t.size % per or t.shape[-2:] != (self.height, self.width):
+            raise ValueError(f"targets of shape {t.shape} are not [frames][batch {self.batch}]"
+                             f"[{self.height}][{self.width}]")
+        f = t.size // per
+        r = None
+        if regions is not None:
+            r = np.ascontiguousarray(np.asarray(regions) != 0, dtype=np.uint8)
+            if r.size != t.size or r.shape[-2:] != (self.height, self.width):
+                raise ValueError(f"regions of shape {r.shape} do not match targets of shape {t.shape}")
+        mk = None
+        if mask is not None:
+            mk = np.ascontiguousarray(mask, dtype=np.float64)
+            if mk.shape != (self.height, self.width):
+                raise ValueError(f"the mask has shape {mk.shape}, the holograms {(self.height, self.width)}")
+        check(self._lib.slm_plan_sequence(self.handle, f, ptr(t), ptr(r), int(loops_first), int(loops), float(tol),
+                                          int(bool(resume)), ptr(mk), float(ct2pi), int(rule), int(bool(frames)),
+                                          int(bool(phases)), int(bool(expected))), "slm_plan_sequence")
+        self._seq = (f, max(int(loops_first), int(loops)))
+
+    def sequence_read(self, frames=True, phases=False, expected=False, stats=True, efficiency=False, iters=True):
+        """(frames uint8 [F][B][H][W], phases and expected float32 [F][B][H][W],
+        stats [F][B][max(loops_first, loops)][4], efficiency
+        [F][B][max(loops_first, loops)] (MRAF), iters int32 [F][B] as read()
+        has them) of the last sequence; None where not asked for."""
+        f, rows = getattr(self, "_seq", None) or (1, 1)
+        fb = (f, self.batch)
+        out_f = np.empty(fb + (self.height, self.width), np.uint8) if frames else None
+        out_p = np.empty(fb + (self.height, self.width), np.float32) if phases else None
+        out_e = np.empty(fb + (self.height, self.width), np.float32) if expected else None
+        out_s = np.empty(fb + (rows, 4), np.float64) if stats else None
+        out_eff = np.empty(fb + (rows,), np.float64) if efficiency else None
+        out_i = np.empty(fb, np.int32) if iters else None
+        check(self._lib.slm_plan_sequence_read(self.handle, ptr(out_f), ptr(out_p), ptr(out_e), ptr(out_s),
+                                               ptr(out_eff), ptr(out_i)), "slm_plan_sequence_read")
+        return out_f, out_p, out_e, out_s, out_eff, out_i
 
     def target_stats(self):
         norm = np.empty(self.batch, np.float64)

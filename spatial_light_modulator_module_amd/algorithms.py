@@ -374,6 +374,110 @@ def run_mraf(targets, regions, loops, mixing=0.4, tol=0.0, ain=None, initial_pha
     return out + (effs,) if return_efficiency else out
 
 
+SEQUENCE_ALGORITHMS = {"gerchberg_saxton": ALGO_GS, "weighted_gerchberg_saxton": ALGO_GSW, "mraf": ALGO_MRAF}
+
+
+def _sequence_inputs(targets, loops_first, loops, algorithm, tol, ain, initial_phase, feedback, mixing, regions,
+                     mask):
+    """run_sequence's argument checks (host only): the device targets
+    [F][B][H][W], their type, the algorithm code and the regions as 0 / 1."""
+    if algorithm not in SEQUENCE_ALGORITHMS:
+        raise ValueError(f"unknown sequence algorithm {algorithm!r}: one of {sorted(SEQUENCE_ALGORITHMS)}")
+    algo = SEQUENCE_ALGORITHMS[algorithm]
+    tdev, tt = target_for_device(targets)
+    if tdev.ndim == 3:
+        tdev = tdev[:, None]
+    if tdev.ndim != 4 or tdev.shape[0] < 1 or tdev.shape[1] < 1:
+        raise ValueError(f"targets must be [F][H][W] or [F][B][H][W] with at least one frame, got shape "
+                         f"{np.asarray(targets).shape}")
+    f, b, h, w = tdev.shape
+    _check_shape(tdev[0, 0])
+    for name, n in (("loops_first", loops_first), ("loops", loops)):
+        if int(n) != n or n < 1:
+            raise ValueError(f"{name} must be an integer >= 1, got {n}")
+    if not (np.isfinite(tol) and tol >= 0):
+        raise ValueError(f"tol must be finite and >= 0, got {tol}")
+    if algo == ALGO_GSW:
+        _check_gsw_shape(h, w)
+        if not (np.isfinite(feedback) and feedback >= 0):
+            raise ValueError(f"feedback must be a finite number >= 0, got {feedback}")
+    sr = None
+    if algo == ALGO_MRAF:
+        if (h not in _lib.SUPPORTED_LENGTHS or w not in _lib.SUPPORTED_LENGTHS
+                or os.environ.get("SLM_ENGINE") == "float64"):
+            raise ValueError(f"{MRAF_SHAPES} (got {h} x {w})")
+        if not (np.isfinite(mixing) and 0 < mixing <= 1):
+            raise ValueError(f"mixing must be in (0, 1], got {mixing}")
+        if regions is None:
+            raise ValueError("an MRAF sequence needs the signal regions of its frames")
+        sr = np.asarray(regions) != 0
+        if sr.ndim == 3:
+            sr = sr[:, None]
+        if sr.shape != tdev.shape:
+            raise ValueError(f"regions of shape {np.asarray(regions).shape} do not match targets of shape "
+                             f"{np.asarray(targets).shape}")
+        for i in range(f):
+            for k in range(b):
+                if not np.any(sr[i, k] & (tdev[i, k] > 0)):
+                    raise ValueError(f"frame {i}: the signal region of hologram {k} holds no pixel with T > 0")
+    elif regions is not None:
+        raise ValueError("regions apply to algorithm 'mraf' only")
+    if ain is not None and np.asarray(ain).shape != (h, w):
+        raise ValueError(f"ain of shape {np.asarray(ain).shape} does not match {(h, w)}")
+    if initial_phase is not None and np.asarray(initial_phase).size != b * h * w:
+        raise ValueError(f"initial_phase of shape {np.asarray(initial_phase).shape} does not match {(b, h, w)}")
+    if mask is not None and np.asarray(mask).shape != (h, w):
+        raise ValueError(f"mask of shape {np.asarray(mask).shape} does not match {(h, w)}")
+    return tdev, tt, algo, sr
+
+
+def run_sequence(targets, loops_first, loops, algorithm="gerchberg_saxton", tol=0.0, ain=None, initial_phase=None,
+                 feedback=1.0, mixing=0.4, regions=None, mask=None, ct2pi=256, rule=_lib.QUANT_PIL,
+                 return_expected=False):
+    """A sequence of image targets [F][H][W] or [F][B][H][W] (moving traps drawn
+    as pictures) as one device-resident chain (slm_plan_sequence): frame 0
+    starts from initial_phase or cold and runs loops_first iterations, every
+    later frame starts from the phase of the frame before it and runs loops;
+    tol > 0 stops a frame on the device. algorithm is "gerchberg_saxton",
+    "weighted_gerchberg_saxton" (feedback) or "mraf" (mixing, regions of the
+    targets' shape). Returns phases float32 [F][B][H][W], the quantised uint8
+    frames [F][B][H][W] (slm_quantize's mask, ct2pi and rule), the errors as a
+    list per frame of a list per hologram, norm [F][B] and the max E used for
+    expected_outcome [F][B]; with return_expected |C|^2 float32 [F][B][H][W] is
+    appended. Targets other than uint8 are carried as float32, with norm and the
+    error's constant term taken from that copy."""
+    tdev, tt, algo, sr = _sequence_inputs(targets, loops_first, loops, algorithm, tol, ain, initial_phase, feedback,
+                                          mixing, regions, mask)
+    f, b, h, w = tdev.shape
+    loops_first, loops = int(loops_first), int(loops)
+    plan = get_plan(algo, b, h, w, tt, ain is not None, max(loops_first, loops))
+    if ain is not None:
+        plan.set_ain(ain)
+    if algo == ALGO_GSW:
+        plan.set_feedback(float(feedback))
+    if algo == ALGO_MRAF:
+        plan.set_mixing(float(mixing))
+    plan.set_phase(initial_phase)
+    plan.sequence(tdev, sr, loops_first=loops_first, loops=loops, tol=tol, mask=mask, ct2pi=ct2pi, rule=rule,
+                  frames=True, phases=True, expected=return_expected)
+    frames, phases, e, stats, _, iters = plan.sequence_read(frames=True, phases=True, expected=return_expected)
+    errs, maxes = [], np.empty((f, b), np.float64)
+    for i in range(f):
+        errs.append([])
+        for k in range(b):
+            n = loops_first if i == 0 else loops
+            if tol > 0 and iters[i, k] >= 0:
+                n = int(iters[i, k])
+            errs[i].append([np.float64(v) for v in stats[i, k, :n, 3]])
+            maxes[i, k] = stats[i, k, n - 1, 0]
+    if sr is None:
+        norm = tdev.reshape(f, b, -1).max(axis=2).astype(np.float64)
+    else:
+        norm = np.where(sr, tdev, 0).reshape(f, b, -1).max(axis=2).astype(np.float64)
+    out = phases, frames, errs, norm, maxes
+    return out + (e,) if return_expected else out
+
+
 def run_gs_multi(targets, loops, devices, tol=0.0, ain=None, feedback=None):
     """run_gs's contract over several GPUs from this one process
     (slm_gs_multi: contiguous shards, one host thread / plan per device).

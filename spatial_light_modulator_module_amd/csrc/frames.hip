@@ -1,6 +1,8 @@
 // SLM frame kernels: single-trap holograms, the
-// quantisation of phase (+ correction mask) to the SLM's 8-bit levels, and the
-// CLI's hologram post-processing (deflecting ramp + lens).
+// quantisation of phase (+ correction mask) to the SLM's 8-bit levels, the
+// CLI's hologram post-processing (deflecting ramp + lens), and the per-frame
+// epilogue of an image sequence (slm_plan_sequence: phase_frame_kernel,
+// frame_rows_kernel; the chain itself is in slm_capi.hip).
 //
 //   transform_hologram src/generate_hologram.py:82-87, 178-203 and
 //                      src/wavefront_correction.py:440-449
@@ -31,6 +33,7 @@
 #include <cstdint>
 #include <mutex>
 
+#include "plan.hpp"
 #include "quantize.hpp"
 #include "runtime.hpp"
 
@@ -119,6 +122,63 @@ __global__ void __launch_bounds__(256) quantize_kernel(const T* src, const doubl
     }
 }
 
+// Per-frame epilogue of an image sequence (slm_plan_sequence): one pass over the
+// run's float32 phase writes the uint8 panel frame (the rules of quantize.hpp,
+// on (double)phase as slm_quantize sees it after hologram_from's widening), the
+// next frame's start phase and, if kept, the frame's phase slice. VEC (holo a
+// multiple of 4, so every slice and the mask are 16-byte aligned): four pixels
+// per lane from one 16-byte load, the mask as two 16-byte loads of float64, the
+// frame as one 4-byte store. 4 B read + 5 .. 9 B written per pixel (+ 8 B of mask).
+template <bool VEC>
+__global__ void __launch_bounds__(256) phase_frame_kernel(const float* __restrict__ phase,
+                                                          const double* __restrict__ mask, long long n,
+                                                          long long holo, double ct2pi, int rule,
+                                                          uint8_t* __restrict__ frame, float* __restrict__ next,
+                                                          float* __restrict__ keep) {
+    const long long stride = (long long)gridDim.x * 256;
+    if constexpr (VEC) {
+        const long long nv = n / 4;  // n = 4 nv exactly
+        for (long long i = blockIdx.x * 256LL + threadIdx.x; i < nv; i += stride) {
+            const float4 q = reinterpret_cast<const float4*>(phase)[i];
+            reinterpret_cast<float4*>(next)[i] = q;
+            if (keep) reinterpret_cast<float4*>(keep)[i] = q;
+            if (!frame) continue;
+            double2 ma = make_double2(0.0, 0.0), mb = ma;
+            if (mask) {
+                const double2* m = reinterpret_cast<const double2*>(mask + (4 * i) % holo);
+                ma = m[0];
+                mb = m[1];
+            }
+            const uint32_t word = (uint32_t)quantize((double)q.x, ma.x, ct2pi, rule) |
+                                  (uint32_t)quantize((double)q.y, ma.y, ct2pi, rule) << 8 |
+                                  (uint32_t)quantize((double)q.z, mb.x, ct2pi, rule) << 16 |
+                                  (uint32_t)quantize((double)q.w, mb.y, ct2pi, rule) << 24;
+            reinterpret_cast<uint32_t*>(frame)[i] = word;
+        }
+    } else {
+        for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += stride) {
+            const float v = phase[i];
+            next[i] = v;
+            if (keep) keep[i] = v;
+            if (frame) frame[i] = quantize((double)v, mask ? mask[i % holo] : 0.0, ct2pi, rule);
+        }
+    }
+}
+
+// the statistics rows (and efficiency rows) a frame can have reached, and its
+// stop words, from the plan's own buffers into the frame's slabs
+__global__ void __launch_bounds__(256) frame_rows_kernel(const double* __restrict__ stats,
+                                                         const double* __restrict__ eff,
+                                                         const int* __restrict__ stop, int max_loops, int rows,
+                                                         double* __restrict__ stats_out,
+                                                         double* __restrict__ eff_out, int* __restrict__ stop_out) {
+    const long long b = blockIdx.x;
+    for (int k = threadIdx.x; k < rows * 4; k += 256) stats_out[b * rows * 4 + k] = stats[b * max_loops * 4 + k];
+    if (eff)
+        for (int k = threadIdx.x; k < rows; k += 256) eff_out[b * rows + k] = eff[b * max_loops + k];
+    if (threadIdx.x == 0) stop_out[b] = stop[b];
+}
+
 // Device scratch reused across calls (frames are small; the interactive loop
 // calls these repeatedly).
 struct Scratch {
@@ -143,6 +203,30 @@ int grid_for(long long n) { return (int)std::min<long long>(8192, (n + 255) / 25
 }  // namespace
 
 using slm::fail;
+
+namespace slm {
+
+int enqueue_phase_frame(hipStream_t st, const float* phase, const double* mask, long long n, long long holo,
+                        double ct2pi, int rule, uint8_t* frame, float* next_start, float* keep) {
+    if (holo % 4 == 0)
+        hipLaunchKernelGGL(phase_frame_kernel<true>, dim3(grid_for(n / 4)), dim3(256), 0, st, phase, mask, n, holo,
+                           ct2pi, rule, frame, next_start, keep);
+    else
+        hipLaunchKernelGGL(phase_frame_kernel<false>, dim3(grid_for(n)), dim3(256), 0, st, phase, mask, n, holo,
+                           ct2pi, rule, frame, next_start, keep);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int enqueue_frame_rows(hipStream_t st, const double* stats, const double* eff, const int* stop, int B, int max_loops,
+                       int rows, double* stats_out, double* eff_out, int* stop_out) {
+    hipLaunchKernelGGL(frame_rows_kernel, dim3(B), dim3(256), 0, st, stats, eff, stop, max_loops, rows, stats_out,
+                       eff_out, stop_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+}  // namespace slm
 
 // the error text is the failed expression alone
 #define FR_TRY(expr)                                                  \

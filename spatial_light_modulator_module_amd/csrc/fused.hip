@@ -740,11 +740,16 @@ struct FusedEngine : Engine {
         const long long n = (long long)s.B * s.holo;
         uint8_t* const stage = reinterpret_cast<uint8_t*>(y);  // scratch between runs
         HIP_TRY(hipMemcpyAsync(stage, region, (size_t)n, hipMemcpyHostToDevice, s.stream));
-        return relayout(layout_x_log2(lid), (const uint8_t*)stage, s.region, n, s.H, s.W, true, s.stream);
+        return land_region_dev(s, stage);
+    }
+
+    // the same from a row-major plane on the device
+    int land_region_dev(PlanState& s, const uint8_t* region) override {
+        return relayout(layout_x_log2(lid), region, s.region, (long long)s.B * s.holo, s.H, s.W, true, s.stream);
     }
 
     int mraf_refresh(PlanState& s, bool reduce, int* bad_holo) override {
-        *bad_holo = -1;
+        if (bad_holo) *bad_holo = -1;
         if (reduce) {
             if (s.tt == SLM_TGT_U8)
                 hipLaunchKernelGGL((mraf_region_kernel<TGT_U8, uint8_t>), dim3(s.B), dim3(kGswThreads), 0, s.stream,
@@ -762,6 +767,7 @@ struct FusedEngine : Engine {
         hipLaunchKernelGGL(mraf_scale_kernel, dim3((s.B + 255) / 256), dim3(256), 0, s.stream, s.mraf,
                            const_cast<double*>(mraf_scales(s.region, s.B, s.holo)), s.B, (double)s.mixing, (double)s.holo, s.has_ain);
         HIP_TRY(hipGetLastError());
+        if (!bad_holo) return 0;  // a sequence: checked on the host up front, enqueued only
         if (reduce) {
             std::vector<double> npos(s.B);
             RC(copy_sync(npos.data(), s.mraf + MRAF_NPOS * s.B, (size_t)s.B * sizeof(double), hipMemcpyDeviceToHost,

@@ -103,7 +103,12 @@ struct Engine {
     // constants of s.mraf from the target, the region, a_in and m (`reduce`: the
     // reductions too, else the two rows that depend on m alone); *bad_holo: the
     // first hologram whose region holds no pixel with T > 0, or -1
+    // land_region_dev: the same from a row-major plane already on the device (a
+    // sequence's uploaded stack). bad_holo == nullptr: the caller has checked
+    // the support itself, and the refresh is enqueued without the copy back
+    // that the check costs (nothing synchronises with the host).
     virtual int land_region(PlanState& s, const uint8_t* region);
+    virtual int land_region_dev(PlanState& s, const uint8_t* region);
     virtual int mraf_refresh(PlanState& s, bool reduce, int* bad_holo);
     // one full run (setup, loops iterations, phase and expected output), on s.stream
     virtual int enqueue(PlanState& s, int loops, double tol, int checked, float wa, bool phase_set,
@@ -176,6 +181,36 @@ int gather_order_after(GatherState& g, hipStream_t stream);
 // waits for queued gathers, frees buffers, events and the comm stream
 void gather_free(GatherState& g);
 
+// The last image sequence of a plan (slm_plan_sequence): the uploaded stacks
+// the chain reads and the per-frame slabs it writes. Sized at the call, only
+// grow, go with the plan.
+struct SeqState {
+    DevBuf<char> targets;      // [F] frames of [B][H][W], each at a 256-byte pitch
+    DevBuf<uint8_t> regions;   // MRAF: the same for the regions
+    DevBuf<double> mask;       // [H][W]
+    DevBuf<float> start;       // [B][H][W]: the phase the last frame ended with = the next frame's start
+    DevBuf<uint8_t> frames;    // [F][B][H][W]
+    DevBuf<float> phases, expected;  // [F][B][H][W]
+    DevBuf<double> stats;      // [F][B][rows][4]
+    DevBuf<double> eff;        // MRAF: [F][B][rows]
+    DevBuf<int> stop;          // [F][B], as PlanState::stop
+    int n_frames = 0;          // of the last sequence (0: none to read)
+    int rows = 0;              // max(loops_first, loops) of the last sequence
+    bool has_frames = false, has_phases = false, has_expected = false;
+    bool resumable = false;    // no slm_plan_set_* and no run since the last sequence
+};
+
+// The per-frame epilogue of a sequence (frames.hip), enqueued on `st`: the
+// run's float32 phase [n] -> the uint8 frame (quantize.hpp; frame may be
+// nullptr), the next frame's start phase, and the kept phase slice (keep may
+// be nullptr). mask [holo] float64 or nullptr.
+int enqueue_phase_frame(hipStream_t st, const float* phase, const double* mask, long long n, long long holo,
+                        double ct2pi, int rule, uint8_t* frame, float* next_start, float* keep);
+// rows 0 .. rows-1 of every hologram's statistics (and efficiency, unless
+// nullptr) and the stop words of the run that just ended -> frame slabs
+int enqueue_frame_rows(hipStream_t st, const double* stats, const double* eff, const int* stop, int B, int max_loops,
+                       int rows, double* stats_out, double* eff_out, int* stop_out);
+
 }  // namespace slm
 
 struct slm_plan {
@@ -191,6 +226,12 @@ struct slm_plan {
     bool weights_fresh = false;  // set_weights since the last run: the plan's weights are weights0 (or ones)
     bool region_set = false;     // MRAF: slm_plan_set_region succeeded
     int mraf_bad = -1;           // MRAF: a hologram whose region holds no pixel with T > 0 (a run refuses it)
+    bool ain_set = false;        // slm_plan_set_ain succeeded
+    // MRAF: the region in force as the caller gave it (a sequence without
+    // regions of its own checks every frame's support against it on the host)
+    std::vector<uint8_t> region_host;
+    slm::SeqState seq;           // slm_plan_sequence
+    bool seq_tail = false;       // a sequence and no run since: slm_plan_read has nothing of a run to return
     // parameters of the last enqueued run (settling a faulted run redoes it)
     int last_loops = 0, last_checked = 0;
     double last_tol = 0.0;

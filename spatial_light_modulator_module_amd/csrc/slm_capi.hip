@@ -1,6 +1,8 @@
 // libslm_hip.so C boundary (include/slm_hip.h): argument checks, the plan's
 // shared buffers, graph capture and replay of a run, HIP-event timing, reads,
-// and the one-shot helpers. The iterations themselves run in an engine
+// image sequences (slm_plan_sequence: frames landed and run as one chain at the
+// Engine interface, their epilogue kernels in frames.hip), and the one-shot
+// helpers. The iterations themselves run in an engine
 // (plan.hpp: fused.hip or generic.hip); the gathers are in comm.hip.
 #include <hip/hip_runtime.h>
 
@@ -79,6 +81,9 @@ int Engine::read_weights(PlanState&, bool, float*) {
     return fail(SLM_ERR_STATE, "weights belong to weighted-GS plans of the fused engine");
 }
 int Engine::land_region(PlanState&, const uint8_t*) {
+    return fail(SLM_ERR_STATE, "a signal region belongs to MRAF plans of the fused engine");
+}
+int Engine::land_region_dev(PlanState&, const uint8_t*) {
     return fail(SLM_ERR_STATE, "a signal region belongs to MRAF plans of the fused engine");
 }
 int Engine::mraf_refresh(PlanState&, bool, int*) {
@@ -256,6 +261,114 @@ int settle(slm_plan* p, bool* redo) {
     RC(e->settle(p->s, redo));
     if (*redo) RC(drop_graph(p));
     return 0;
+}
+
+// ---- image sequences (slm_plan_sequence) ----
+
+constexpr size_t kSeqPitch = 256;  // every frame of an uploaded stack starts as aligned as a lone upload does
+inline size_t seq_pitch(size_t bytes) { return (bytes + kSeqPitch - 1) / kSeqPitch * kSeqPitch; }
+
+// a host stack of n_frames slices to the device, one slice per pitch
+int seq_upload(char* dst, const void* src, size_t slice, size_t n_frames, hipStream_t st) {
+    const size_t pitch = seq_pitch(slice);
+    if (pitch == slice) {
+        HIP_TRY(hipMemcpyAsync(dst, src, slice * n_frames, hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    for (size_t f = 0; f < n_frames; ++f)
+        HIP_TRY(hipMemcpyAsync(dst + f * pitch, static_cast<const char*>(src) + f * slice, slice,
+                               hipMemcpyHostToDevice, st));
+    return 0;
+}
+
+// MRAF: the first (frame, hologram) whose region holds no pixel with T > 0.
+// regions == nullptr: `fixed` [B][holo] serves every frame.
+template <typename TT>
+bool seq_mraf_unsupported(const PlanState& s, int n_frames, const void* targets, const uint8_t* regions,
+                          const uint8_t* fixed, int* frame, int* holo) {
+    const size_t n = (size_t)s.holo;
+    for (int f = 0; f < n_frames; ++f)
+        for (int b = 0; b < s.B; ++b) {
+            const size_t k = (size_t)f * s.B + b;
+            const TT* t = static_cast<const TT*>(targets) + k * n;
+            const uint8_t* r = regions ? regions + k * n : fixed + (size_t)b * n;
+            size_t i = 0;
+            while (i < n && !(r[i] && t[i] > 0)) ++i;
+            if (i == n) {
+                *frame = f;
+                *holo = b;
+                return true;
+            }
+        }
+    return false;
+}
+
+// slm_plan_set_target (and slm_plan_set_region) of frame f from the uploaded
+// stacks, enqueued only: the same kernels on the same bytes
+int seq_land(slm_plan* p, Engine* e, const char* tgt, const uint8_t* region) {
+    PlanState& s = p->s;
+    // an engine that reads the target where it was staged keeps it there
+    if (e->target_stage(s) == s.tgt) {
+        HIP_TRY(hipMemcpyAsync(s.tgt, tgt, (size_t)s.B * s.holo * (s.tt == SLM_TGT_U8 ? 1 : 4),
+                               hipMemcpyDeviceToDevice, s.stream));
+        tgt = static_cast<const char*>(s.tgt);
+    }
+    if (s.tt == SLM_TGT_U8)
+        target_stats_partial<uint8_t>(p, tgt);
+    else
+        target_stats_partial<float>(p, tgt);
+    RC(e->land_target(s, tgt));
+    hipLaunchKernelGGL(target_stats_final_kernel, dim3(s.B), dim3(kTsThreads), 0, s.stream, p->ts_part,
+                       ts_blocks(s.holo), s.norm, s.normf, s.sum_t2);
+    HIP_TRY(hipGetLastError());
+    if (s.algo != SLM_ALGO_MRAF) return 0;
+    if (region) RC(e->land_region_dev(s, region));
+    return e->mraf_refresh(s, true, nullptr);
+}
+
+struct SeqArgs {
+    int n_frames, loops_first, loops, resume, rule;
+    double tol, ct2pi;
+    bool regions, mask, want_frames, want_phases, want_expected;
+};
+
+// The chain: per frame the landing, the run from the previous frame's phase,
+// and the epilogue into the frame's slabs. Nothing here waits for the device.
+int seq_enqueue(slm_plan* p, Engine* e, const SeqArgs& a) {
+    PlanState& s = p->s;
+    SeqState& q = p->seq;
+    const size_t n = (size_t)s.B * s.holo, tpitch = seq_pitch(n * (s.tt == SLM_TGT_U8 ? 1 : 4)), rpitch = seq_pitch(n);
+    const bool mraf = s.algo == SLM_ALGO_MRAF;
+    // the caller's start phase stays in force after the sequence: frames f > 0
+    // read the chain's own buffer in its place
+    float* const caller_phase = s.phase_in;
+    const bool caller_set = p->phase_set;
+    int rc = 0;
+    for (int f = 0; f < a.n_frames && !rc; ++f) {
+        rc = seq_land(p, e, q.targets.p + (size_t)f * tpitch, a.regions ? q.regions.p + (size_t)f * rpitch : nullptr);
+        if (rc) break;
+        const bool chained = f > 0 || a.resume;
+        s.phase_in = chained ? q.start.p : caller_phase;
+        p->phase_set = chained || caller_set;
+        rc = enqueue_run(p, chained ? a.loops : a.loops_first, a.tol, a.tol > 0.0 ? 1 : 0, 0.f);
+        if (rc) break;
+        const size_t fb = (size_t)f * s.B;
+        rc = enqueue_phase_frame(s.stream, s.phase_out, a.mask ? q.mask.p : nullptr, (long long)n, s.holo, a.ct2pi,
+                                 a.rule, a.want_frames ? q.frames.p + fb * s.holo : nullptr, q.start.p,
+                                 a.want_phases ? q.phases.p + fb * s.holo : nullptr);
+        if (rc) break;
+        if (a.want_expected) {
+            const hipError_t err = hipMemcpyAsync(q.expected.p + fb * s.holo, s.e_out, n * sizeof(float),
+                                                  hipMemcpyDeviceToDevice, s.stream);
+            if (err != hipSuccess) rc = fail(SLM_ERR_HIP, "sequence: copy of E failed: %s", hipGetErrorString(err));
+            if (rc) break;
+        }
+        rc = enqueue_frame_rows(s.stream, s.stats, mraf ? s.eff : nullptr, s.stop, s.B, s.max_loops, q.rows,
+                                q.stats.p + fb * q.rows * 4, mraf ? q.eff.p + fb * q.rows : nullptr, q.stop.p + fb);
+    }
+    s.phase_in = caller_phase;
+    p->phase_set = caller_set;
+    return rc;
 }
 
 void free_plan(slm_plan* p) {
@@ -558,6 +671,7 @@ int slm_plan_set_target(slm_plan* p, const void* tgt) {
     Engine* e = nullptr;
     RC(engine_of(p, &e));
     PlanState& s = p->s;
+    p->seq.resumable = false;
     HIP_TRY(hipSetDevice(s.device));
     const size_t bytes = (size_t)s.B * s.holo * (s.tt == SLM_TGT_U8 ? 1 : 4);
     void* stage = e->target_stage(s);
@@ -589,6 +703,7 @@ int slm_plan_set_precision(slm_plan* p, int precision) {
     Engine* e = nullptr;
     RC(engine_of(p, &e));
     PlanState& s = p->s;
+    p->seq.resumable = false;
     HIP_TRY(hipSetDevice(s.device));
     if (!p->any_size) {  // in place: the plan keeps its layout pair
         RC(drop_graph(p));
@@ -627,6 +742,8 @@ int slm_plan_set_ain(slm_plan* p, const float* ain) {
     // before its DMA has landed.
     HIP_TRY(hipMemcpyAsync(p->s.ain, ain, (size_t)p->s.holo * sizeof(float), hipMemcpyHostToDevice, p->s.stream));
     HIP_TRY(hipStreamSynchronize(p->s.stream));
+    p->ain_set = true;
+    p->seq.resumable = false;
     return mraf_update(p, true);
 }
 
@@ -634,6 +751,7 @@ int slm_plan_set_phase(slm_plan* p, const float* phase) {
     if (!p) return fail(SLM_ERR_ARG, "null plan");
     PlanState& s = p->s;
     if (!gs_like(s.algo)) return fail(SLM_ERR_STATE, "initial phase applies to GS plans");
+    p->seq.resumable = false;
     HIP_TRY(hipSetDevice(s.device));
     if (!phase) {
         p->phase_set = false;
@@ -670,6 +788,7 @@ int slm_plan_set_feedback(slm_plan* p, float feedback) {
         return fail(SLM_ERR_ARG, "feedback exponent %g is not a finite number >= 0", (double)feedback);
     if (p->s.algo != SLM_ALGO_GSW) return fail(SLM_ERR_STATE, "the feedback exponent applies to weighted-GS plans");
     p->s.feedback = feedback;
+    p->seq.resumable = false;
     return 0;
 }
 
@@ -679,6 +798,7 @@ int slm_plan_set_weights(slm_plan* p, const float* w) {
     if (s.algo != SLM_ALGO_GSW) return fail(SLM_ERR_STATE, "weights apply to weighted-GS plans");
     Engine* e = nullptr;
     RC(engine_of(p, &e));
+    p->seq.resumable = false;
     HIP_TRY(hipSetDevice(s.device));
     if (!w) {
         s.weights_set = false;
@@ -723,9 +843,11 @@ int slm_plan_set_region(slm_plan* p, const uint8_t* region) {
     HIP_TRY(hipStreamSynchronize(s.stream));  // the staging buffer is scratch of a queued run
     p->region_set = false;
     p->mraf_bad = -1;
+    p->seq.resumable = false;
     RC(e->land_region(s, region));
     HIP_TRY(hipStreamSynchronize(s.stream));
     p->region_set = true;
+    p->region_host.assign(region, region + (size_t)s.B * s.holo);
     RC(mraf_update(p, true));
     if (p->mraf_bad >= 0) {
         p->region_set = false;
@@ -740,6 +862,7 @@ int slm_plan_set_mixing(slm_plan* p, float m) {
     if (p->s.algo != SLM_ALGO_MRAF) return fail(SLM_ERR_STATE, "the mixing parameter applies to MRAF plans");
     HIP_TRY(hipSetDevice(p->s.device));
     p->s.mixing = m;
+    p->seq.resumable = false;
     return mraf_update(p, false);
 }
 
@@ -769,6 +892,8 @@ int slm_plan_run(slm_plan* p, int loops, double tol, int checked, float wa) {
     RC(mraf_ready(p));
     p->field_fresh = false;  // replays skip enqueue_run
     p->weights_fresh = false;
+    p->seq.resumable = false;
+    p->seq_tail = false;
     p->last_loops = loops;
     p->last_tol = tol;
     p->last_checked = checked;
@@ -829,6 +954,8 @@ int slm_plan_run_timed(slm_plan* p, int loops, double tol, int checked, float wa
         HIP_TRY(hipGetLastError());
     }
     p->events.used = 0;
+    p->seq.resumable = false;
+    p->seq_tail = false;
     s.timing = &p->events;
     int rc = enqueue_run(p, loops, tol, checked, wa);
     s.timing = nullptr;
@@ -892,6 +1019,8 @@ int slm_plan_marked_ms(slm_plan* p, double* ms) {
 
 int slm_plan_read(slm_plan* p, float* phase, float* expected, double* stats, int* iters) {
     if (!p) return fail(SLM_ERR_ARG, "null plan");
+    if (p->seq_tail)
+        return fail(SLM_ERR_STATE, "no run since the last sequence (its results: slm_plan_sequence_read)");
     RC(slm_plan_sync(p));
     PlanState& s = p->s;
     const size_t n = (size_t)s.B * s.holo;
@@ -920,6 +1049,7 @@ int slm_plan_set_target_stats(slm_plan* p, const double* norm, const double* sum
     if (!p || !norm || !sum_t2) return fail(SLM_ERR_ARG, "null argument");
     if (!p->target_set) return fail(SLM_ERR_STATE, "target not set");
     PlanState& s = p->s;
+    p->seq.resumable = false;
     HIP_TRY(hipSetDevice(s.device));
     std::vector<float> nf(s.B);
     for (int b = 0; b < s.B; ++b) nf[b] = (float)norm[b];
@@ -927,6 +1057,113 @@ int slm_plan_set_target_stats(slm_plan* p, const double* norm, const double* sum
     HIP_TRY(hipMemcpyAsync(s.normf, nf.data(), (size_t)s.B * sizeof(float), hipMemcpyHostToDevice, s.stream));
     HIP_TRY(hipMemcpyAsync(s.sum_t2, sum_t2, (size_t)s.B * sizeof(double), hipMemcpyHostToDevice, s.stream));
     HIP_TRY(hipStreamSynchronize(s.stream));
+    return 0;
+}
+
+int slm_plan_sequence(slm_plan* p, int n_frames, const void* targets, const uint8_t* regions, int loops_first,
+                      int loops, double tol, int resume, const double* mask, double ct2pi, int rule, int want_frames,
+                      int want_phases, int want_expected) {
+    if (!p || !targets) return fail(SLM_ERR_ARG, "null argument");
+    Engine* e = nullptr;
+    RC(engine_of(p, &e));
+    PlanState& s = p->s;
+    SeqState& q = p->seq;
+    if (n_frames < 1) return fail(SLM_ERR_ARG, "%d frames: a sequence has at least one", n_frames);
+    if (loops_first < 1 || loops_first > s.max_loops || loops < 1 || loops > s.max_loops)
+        return fail(SLM_ERR_ARG, "loops_first %d and loops %d must lie in 1 .. max_loops %d", loops_first, loops,
+                    s.max_loops);
+    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(SLM_ERR_ARG, "tol must be finite and >= 0, got %g", tol);
+    if (rule != SLM_QUANT_ASTYPE && rule != SLM_QUANT_PIL) return fail(SLM_ERR_ARG, "unknown rule %d", rule);
+    if (!(ct2pi > 0.0) || !std::isfinite(ct2pi))
+        return fail(SLM_ERR_ARG, "ct2pi must be finite and positive, got %g", ct2pi);
+    const bool mraf = s.algo == SLM_ALGO_MRAF;
+    if (!gs_like(s.algo)) return fail(SLM_ERR_STATE, "sequences run on GS, weighted-GS and MRAF plans, not on GD plans");
+    if (s.has_ain && !p->ain_set) return fail(SLM_ERR_STATE, "slm_plan_sequence before slm_plan_set_ain");
+    if (regions && !mraf) return fail(SLM_ERR_STATE, "regions apply to MRAF plans");
+    if (mraf && !regions && !p->region_set)
+        return fail(SLM_ERR_STATE, "an MRAF sequence needs regions, or a region in force (slm_plan_set_region)");
+    if (resume && !q.resumable)
+        return fail(SLM_ERR_STATE, "resume needs a previous sequence on this plan with no slm_plan_set_* or run since");
+    if (mraf) {
+        int f = 0, b = 0;
+        const bool bad = s.tt == SLM_TGT_U8
+                             ? seq_mraf_unsupported<uint8_t>(s, n_frames, targets, regions, p->region_host.data(), &f, &b)
+                             : seq_mraf_unsupported<float>(s, n_frames, targets, regions, p->region_host.data(), &f, &b);
+        if (bad)
+            return fail(SLM_ERR_ARG, "frame %d: the signal region of hologram %d holds no pixel with T > 0", f, b);
+    }
+    HIP_TRY(hipSetDevice(s.device));
+
+    // ---- buffers, sized for this call ----
+    const size_t F = (size_t)n_frames, n = (size_t)s.B * s.holo, tbytes = n * (s.tt == SLM_TGT_U8 ? 1 : 4);
+    const int rows = std::max(loops_first, loops);
+    q.n_frames = 0;  // nothing to read, and nothing to resume from, if this call fails half way
+    q.resumable = false;
+    RC(q.targets.need(F * seq_pitch(tbytes), s.stream));
+    if (regions) RC(q.regions.need(F * seq_pitch(n), s.stream));
+    if (want_frames && mask) RC(q.mask.need((size_t)s.holo * sizeof(double), s.stream));
+    RC(q.start.need(n * sizeof(float), s.stream));
+    if (want_frames) RC(q.frames.need(F * n, s.stream));
+    if (want_phases) RC(q.phases.need(F * n * sizeof(float), s.stream));
+    if (want_expected) RC(q.expected.need(F * n * sizeof(float), s.stream));
+    RC(q.stats.need(F * s.B * rows * 4 * sizeof(double), s.stream));
+    if (mraf) RC(q.eff.need(F * s.B * rows * sizeof(double), s.stream));
+    RC(q.stop.need(F * s.B * sizeof(int), s.stream));
+
+    // ---- everything the chain reads goes up once, and has landed before the first launch ----
+    RC(seq_upload(q.targets.p, targets, tbytes, F, s.stream));
+    if (regions) RC(seq_upload(reinterpret_cast<char*>(q.regions.p), regions, n, F, s.stream));
+    if (want_frames && mask)
+        HIP_TRY(hipMemcpyAsync(q.mask.p, mask, (size_t)s.holo * sizeof(double), hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipStreamSynchronize(s.stream));
+
+    // ---- the plan is as after slm_plan_set_target (and _set_region) with the last frame ----
+    p->target_set = true;
+    s.weights_set = false;  // weighted GS: every frame starts from ones, as after slm_plan_set_target
+    p->weights_fresh = false;
+    if (regions) {
+        const uint8_t* last = regions + (F - 1) * n;
+        p->region_host.assign(last, last + n);
+        p->region_set = true;
+    }
+    p->mraf_bad = -1;  // checked above, frame by frame
+
+    const SeqArgs a{n_frames, loops_first, loops, resume, rule, tol, ct2pi, regions != nullptr,
+                    want_frames && mask, want_frames != 0, want_phases != 0, want_expected != 0};
+    q.rows = rows;
+    RC(seq_enqueue(p, e, a));
+    q.n_frames = n_frames;
+    q.has_frames = want_frames != 0;
+    q.has_phases = want_phases != 0;
+    q.has_expected = want_expected != 0;
+    q.resumable = true;
+    p->seq_tail = true;
+    return 0;
+}
+
+int slm_plan_sequence_read(slm_plan* p, unsigned char* frames, float* phases, float* expected, double* stats,
+                           double* efficiency, int* iters) {
+    if (!p) return fail(SLM_ERR_ARG, "null plan");
+    PlanState& s = p->s;
+    const SeqState& q = p->seq;
+    if (!q.n_frames) return fail(SLM_ERR_STATE, "slm_plan_sequence_read before a sequence");
+    if (frames && !q.has_frames) return fail(SLM_ERR_STATE, "the sequence was run without frames");
+    if (phases && !q.has_phases) return fail(SLM_ERR_STATE, "the sequence was run without phases");
+    if (expected && !q.has_expected) return fail(SLM_ERR_STATE, "the sequence was run without expected outputs");
+    if (efficiency && s.algo != SLM_ALGO_MRAF)
+        return fail(SLM_ERR_STATE, "the efficiency is a statistic of MRAF plans");
+    HIP_TRY(hipSetDevice(s.device));
+    HIP_TRY(hipStreamSynchronize(s.stream));
+    const size_t fb = (size_t)q.n_frames * s.B, n = fb * s.holo;
+    if (frames) RC(copy_sync(frames, q.frames.p, n, hipMemcpyDeviceToHost, s.stream));
+    if (phases) RC(copy_sync(phases, q.phases.p, n * sizeof(float), hipMemcpyDeviceToHost, s.stream));
+    if (expected) RC(copy_sync(expected, q.expected.p, n * sizeof(float), hipMemcpyDeviceToHost, s.stream));
+    if (stats) RC(copy_sync(stats, q.stats.p, fb * q.rows * 4 * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+    if (efficiency) RC(copy_sync(efficiency, q.eff.p, fb * q.rows * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+    if (iters) {
+        RC(copy_sync(iters, q.stop.p, fb * sizeof(int), hipMemcpyDeviceToHost, s.stream));
+        stop_to_iterations(iters, (long long)fb);
+    }
     return 0;
 }
 

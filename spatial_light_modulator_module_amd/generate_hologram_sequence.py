@@ -25,9 +25,10 @@ import numpy as np
 from . import parallel
 from . import _lib
 from .algorithms import (_check_shape, _print_loops, expected_from, hologram_from, incoming_amplitude, run_gs,
-                         run_gs_multi, run_gsw)
+                         run_gs_multi, run_gsw, run_sequence)
 
 SEQ_BATCH = int(os.environ.get("SLM_SEQ_BATCH", "64"))  # frames per GPU launch batch
+SEQ_CHAIN = int(os.environ.get("SLM_SEQ_CHAIN", "256"))  # frames per enqueued chain (--chain)
 
 
 def _load_frame(source_dir_path, i):
@@ -47,6 +48,52 @@ def _batches(indices, frames):
         run.append(i)
     if run:
         yield run
+
+
+def _chains(indices, frames):
+    """Split an index list into runs of consecutive frames of equal shape and dtype."""
+    run = []
+    for i in indices:
+        if run and (i != run[-1] + 1 or frames[i].shape != frames[run[0]].shape
+                    or frames[i].dtype != frames[run[0]].dtype):
+            yield run
+            run = []
+        run.append(i)
+    if run:
+        yield run
+
+
+def _chained(args, mine, frames, dest_dir_holograms, dest_dir_preview):
+    """--chain: this rank's frames as device-resident chains (run_sequence):
+    every frame after the first of a run starts from the phase of the frame
+    before it. A run longer than SEQ_CHAIN goes in pieces, each continued from
+    the last phase of the piece before it, which is the uncut chain."""
+    from PIL import Image
+
+    algorithm = getattr(args, "algorithm", "gerchberg_saxton")
+    feedback = float(getattr(args, "feedback", 1.0))
+    errors = {}
+    for run in _chains(mine, frames):
+        _check_shape(frames[run[0]])
+        ain = incoming_amplitude(args, frames[run[0]].shape)
+        if not (args.max_loops > 0 and (args.tolerance + 1) > args.tolerance):
+            raise UnboundLocalError("local variable 'expected_outcome' referenced before assignment")
+        last = None
+        for at in range(0, len(run), SEQ_CHAIN):
+            idx = run[at:at + SEQ_CHAIN]
+            stack = np.stack([frames[i] for i in idx])
+            phase, _, errs, norm, emax, e = run_sequence(stack, args.max_loops, args.max_loops, algorithm,
+                                                         args.tolerance, ain, last, feedback, return_expected=True)
+            last = phase[-1]
+            for k, i in enumerate(idx):
+                sys.stdout.write(f"\rcreating {i}. hologram ")
+                _print_loops(len(errs[k][0]), args.max_loops)
+                errors[i] = errs[k][0]
+                np.save(f"{dest_dir_holograms}/{i}.npy", hologram_from(phase[k, 0]))
+                if args.preview:
+                    expected = expected_from(e[k, 0], norm[k, 0], emax[k, 0])
+                    Image.fromarray(expected).convert("L").save(f"{dest_dir_preview}/{i}.png")
+    return errors
 
 
 def multi_devices(nranks):
@@ -77,6 +124,8 @@ def generate_hologram_sequence(args, rank=None, nranks=None):
     mine = list(parallel.shard_range(n_files, nranks, rank))
     frames = {i: _load_frame(source_dir_path, i) for i in mine}
     errors = {}
+    if getattr(args, "chain", False):
+        return _chained(args, mine, frames, dest_dir_holograms, dest_dir_preview)
     devices = multi_devices(nranks)
     for idx in _batches(mine, frames):
         stack = np.stack([frames[i] for i in idx])
@@ -134,6 +183,9 @@ def build_parser():
                    help="algorithm (weighted_gerchberg_saxton evens out the trap intensities)")
     p.add_argument("--feedback", metavar="FLOAT", default=1.0, type=float,
                    help="weight feedback exponent of weighted_gerchberg_saxton")
+    p.add_argument("--chain", action="store_true",
+                   help="run consecutive frames as one device-resident chain, each frame starting from the phase of "
+                        "the frame before it (no reference counterpart)")
     return p
 
 
