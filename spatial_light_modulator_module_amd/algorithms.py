@@ -208,6 +208,41 @@ def _stop_index(err, tol):
     return int(np.argmax(bad)) if bad.any() else None
 
 
+def _run(plan, loops, tol, *white_attention):
+    """Run a prepared plan and read it back: (phase, e, stats, iters, checked).
+    tol > 0 runs with device checks. Any other run is speculative and
+    unchecked: "while error > tolerance" is rechecked on the host, and a
+    hologram that should have stopped early is rerun with device checks."""
+    checked = tol > 0
+    plan.run(loops, tol, checked, *white_attention)
+    phase, e, stats, iters = plan.read()
+    if not checked and any(_stop_index(stats[k, :loops, 3], tol) not in (None, loops - 1)
+                           for k in range(plan.batch)):
+        plan.run(loops, tol, True, *white_attention)
+        phase, e, stats, iters = plan.read()
+        checked = True
+    return phase, e, stats, iters, checked
+
+
+def _errors(stats, iters, loops, checked):
+    """Statistics to results: per hologram the errors of the iterations it
+    ran (iters[k] of them where a checked run stopped it, else all `loops`) and
+    the max E of the last of them, which scales expected_outcome."""
+    errs, maxes = [], []
+    for k in range(len(iters)):
+        n = int(iters[k]) if checked and iters[k] >= 0 else loops
+        errs.append([np.float64(v) for v in stats[k, :n, 3]])
+        maxes.append(stats[k, n - 1, 0])
+    return errs, np.array(maxes)
+
+
+def _collect(plan, loops, run):
+    """run_gs's return values from _run's; the norm is the one the plan holds."""
+    phase, e, stats, iters, checked = run
+    errs, maxes = _errors(stats, iters, loops, checked)
+    return phase, e, errs, plan.target_stats()[0], maxes
+
+
 def run_gs(targets, loops, tol=0.0, ain=None, initial_phase=None):
     """GS on a batch [B][H][W] (uint8 or float). Returns phase float32 [B][H][W],
     |C|^2 float32 [B][H][W], errors list per hologram, norm [B], max E used
@@ -221,29 +256,33 @@ def run_gs(targets, loops, tol=0.0, ain=None, initial_phase=None):
     if ain is not None:
         plan.set_ain(ain)
     plan.set_phase(initial_phase)
-    checked = tol > 0
-    plan.run(loops, tol, checked)
-    phase, e, stats, iters = plan.read()
-    if not checked:
-        # speculative unchecked run: recheck "while error > tolerance" on the host;
-        # a hologram that should have stopped early is rerun with device checks.
-        if any(_stop_index(stats[k, :loops, 3], tol) not in (None, loops - 1) for k in range(b)):
-            plan.run(loops, tol, True)
-            phase, e, stats, iters = plan.read()
-            checked = True
-    return _collect(plan, phase, e, stats, iters, loops, checked)
+    return _collect(plan, loops, _run(plan, loops, tol))
 
 
-GSW_SHAPES = ("weighted Gerchberg-Saxton runs on the fused engine only: both sides of the target must be one of "
-              "64, 128, 256, 512, 1024, 2048, 4096 (powers of two) or 768, and $SLM_ENGINE=float64 must not be set")
+_FUSED_ONLY = ("{} runs on the fused engine only: both sides of the target must be one of "
+               "64, 128, 256, 512, 1024, 2048, 4096 (powers of two) or 768, and $SLM_ENGINE=float64 must not be set")
+_GSW, _MRAF = "weighted Gerchberg-Saxton", "MRAF"
+GSW_SHAPES, MRAF_SHAPES = _FUSED_ONLY.format(_GSW), _FUSED_ONLY.format(_MRAF)
 
 
-def _check_gsw_shape(h, w):
-    """Weighted GS is built into the fused engine's column pass; the any-size
-    engines (other sides, $SLM_ENGINE=float64) refuse it."""
-    if (h not in _lib.SUPPORTED_LENGTHS or w not in _lib.SUPPORTED_LENGTHS
+def _fused_only(name, h, w, unsupported=None):
+    """Weighted GS and MRAF (`name`) are built into the fused engine's column
+    pass; the any-size engines (other sides, $SLM_ENGINE=float64) refuse them.
+    Checked before any device call; `unsupported` is the engine's own refusal,
+    which is reported as the same error."""
+    if (unsupported is not None or h not in _lib.SUPPORTED_LENGTHS or w not in _lib.SUPPORTED_LENGTHS
             or os.environ.get("SLM_ENGINE") == "float64"):
-        raise ValueError(f"{GSW_SHAPES} (got {h} x {w})")
+        raise ValueError(f"{_FUSED_ONLY.format(name)} (got {h} x {w})") from unsupported
+
+
+def _fused_plan(name, algo, b, h, w, tt, has_ain, loops):
+    """get_plan for an algorithm that only the fused engine runs."""
+    try:
+        return get_plan(algo, b, h, w, tt, has_ain, loops)
+    except _lib.SlmError as e:
+        if e.code == _lib.ERR_UNSUPPORTED:
+            _fused_only(name, h, w, e)
+        raise
 
 
 def run_gsw(targets, loops, feedback=1.0, tol=0.0, ain=None, initial_phase=None, initial_weights=None,
@@ -256,16 +295,11 @@ def run_gsw(targets, loops, feedback=1.0, tol=0.0, ain=None, initial_phase=None,
     t = np.asarray(targets)
     tdev, tt = target_for_device(t)
     b, h, w = tdev.shape
-    _check_gsw_shape(h, w)
+    _fused_only(_GSW, h, w)
     feedback = float(feedback)
     if not (np.isfinite(feedback) and feedback >= 0):
         raise ValueError(f"feedback must be a finite number >= 0, got {feedback}")
-    try:
-        plan = get_plan(ALGO_GSW, b, h, w, tt, ain is not None, loops)
-    except _lib.SlmError as e:
-        if e.code == _lib.ERR_UNSUPPORTED:
-            raise ValueError(f"{GSW_SHAPES} (got {h} x {w})") from e
-        raise
+    plan = _fused_plan(_GSW, ALGO_GSW, b, h, w, tt, ain is not None, loops)
     plan.set_target(tdev)
     _exact_target_stats(plan, t)
     if ain is not None:
@@ -278,20 +312,8 @@ def run_gsw(targets, loops, feedback=1.0, tol=0.0, ain=None, initial_phase=None,
         if e.code == _lib.ERR_ARG:
             raise ValueError("initial weights must be positive and finite wherever the target is > 0") from e
         raise
-    checked = tol > 0
-    plan.run(loops, tol, checked)
-    phase, e, stats, iters = plan.read()
-    if not checked:
-        if any(_stop_index(stats[k, :loops, 3], tol) not in (None, loops - 1) for k in range(b)):
-            plan.run(loops, tol, True)
-            phase, e, stats, iters = plan.read()
-            checked = True
-    out = _collect(plan, phase, e, stats, iters, loops, checked)
+    out = _collect(plan, loops, _run(plan, loops, tol))
     return out + (plan.read_weights(),) if return_weights else out
-
-
-MRAF_SHAPES = ("MRAF runs on the fused engine only: both sides of the target must be one of "
-               "64, 128, 256, 512, 1024, 2048, 4096 (powers of two) or 768, and $SLM_ENGINE=float64 must not be set")
 
 
 def signal_region(target, margin=8):
@@ -312,6 +334,19 @@ def signal_region(target, margin=8):
     return out.astype(np.uint8)
 
 
+def _check_mixing(mixing):
+    if not (np.isfinite(mixing) and 0 < mixing <= 1):
+        raise ValueError(f"mixing must be in (0, 1], got {mixing}")
+
+
+def _check_support(sr, tdev, where=""):
+    """Every hologram of a batch (sr and tdev are [B][H][W]) needs a target
+    pixel inside its signal region; `where` names the batch in the message."""
+    for k in range(len(tdev)):
+        if not np.any(sr[k] & (tdev[k] > 0)):
+            raise ValueError(f"{where}the signal region of hologram {k} holds no pixel with T > 0")
+
+
 def run_mraf(targets, regions, loops, mixing=0.4, tol=0.0, ain=None, initial_phase=None, return_efficiency=False):
     """MRAF, mixed-region amplitude freedom (no reference counterpart;
     include/slm_hip.h), on a batch [B][H][W]: GS whose amplitude constraint
@@ -325,53 +360,33 @@ def run_mraf(targets, regions, loops, mixing=0.4, tol=0.0, ain=None, initial_pha
     if tdev.ndim != 3:
         raise ValueError(f"targets must be [B][H][W], got shape {tdev.shape}")
     b, h, w = tdev.shape
-    if (h not in _lib.SUPPORTED_LENGTHS or w not in _lib.SUPPORTED_LENGTHS
-            or os.environ.get("SLM_ENGINE") == "float64"):
-        raise ValueError(f"{MRAF_SHAPES} (got {h} x {w})")
+    _fused_only(_MRAF, h, w)
     mixing = float(mixing)
-    if not (np.isfinite(mixing) and 0 < mixing <= 1):
-        raise ValueError(f"mixing must be in (0, 1], got {mixing}")
+    _check_mixing(mixing)
     r = np.asarray(regions)
     if r.shape != tdev.shape:
         raise ValueError(f"regions of shape {r.shape} do not match targets of shape {tdev.shape}")
     sr = r != 0
-    for k in range(b):
-        if not np.any(sr[k] & (tdev[k] > 0)):
-            raise ValueError(f"the signal region of hologram {k} holds no pixel with T > 0")
+    _check_support(sr, tdev)
     if ain is not None and np.asarray(ain).shape != (h, w):
         raise ValueError(f"ain of shape {np.asarray(ain).shape} does not match {(h, w)}")
     if initial_phase is not None and np.asarray(initial_phase).shape != tdev.shape:
         raise ValueError(f"initial_phase of shape {np.asarray(initial_phase).shape} does not match {tdev.shape}")
-    try:
-        plan = get_plan(ALGO_MRAF, b, h, w, tt, ain is not None, loops)
-    except _lib.SlmError as e:
-        if e.code == _lib.ERR_UNSUPPORTED:
-            raise ValueError(f"{MRAF_SHAPES} (got {h} x {w})") from e
-        raise
+    plan = _fused_plan(_MRAF, ALGO_MRAF, b, h, w, tt, ain is not None, loops)
     plan.set_target(tdev)
     plan.set_region(sr)
     if ain is not None:
         plan.set_ain(ain)
     plan.set_mixing(mixing)
     plan.set_phase(initial_phase)
-    checked = tol > 0
-    plan.run(loops, tol, checked)
-    phase, e, stats, iters = plan.read()
-    if not checked:
-        if any(_stop_index(stats[k, :loops, 3], tol) not in (None, loops - 1) for k in range(b)):
-            plan.run(loops, tol, True)
-            phase, e, stats, iters = plan.read()
-            checked = True
-    errs, maxes, effs = [], [], []
+    phase, e, stats, iters, checked = _run(plan, loops, tol)
     eff = plan.read_efficiency()
-    for k in range(b):
-        n = loops if (not checked or iters[k] < 0) else int(iters[k])
-        errs.append([np.float64(v) for v in stats[k, :n, 3]])
-        maxes.append(stats[k, n - 1, 0])
-        effs.append([np.float64(v) for v in eff[k, :n]])
+    errs, maxes = _errors(stats, iters, loops, checked)
     norm = np.array([np.float64(tdev[k][sr[k]].max()) for k in range(b)])
-    out = phase, e, errs, norm, np.array(maxes)
-    return out + (effs,) if return_efficiency else out
+    out = phase, e, errs, norm, maxes
+    if return_efficiency:
+        out += ([[np.float64(v) for v in eff[k, :len(errs[k])]] for k in range(b)],)
+    return out
 
 
 SEQUENCE_ALGORITHMS = {"gerchberg_saxton": ALGO_GS, "weighted_gerchberg_saxton": ALGO_GSW, "mraf": ALGO_MRAF}
@@ -398,16 +413,13 @@ def _sequence_inputs(targets, loops_first, loops, algorithm, tol, ain, initial_p
     if not (np.isfinite(tol) and tol >= 0):
         raise ValueError(f"tol must be finite and >= 0, got {tol}")
     if algo == ALGO_GSW:
-        _check_gsw_shape(h, w)
+        _fused_only(_GSW, h, w)
         if not (np.isfinite(feedback) and feedback >= 0):
             raise ValueError(f"feedback must be a finite number >= 0, got {feedback}")
     sr = None
     if algo == ALGO_MRAF:
-        if (h not in _lib.SUPPORTED_LENGTHS or w not in _lib.SUPPORTED_LENGTHS
-                or os.environ.get("SLM_ENGINE") == "float64"):
-            raise ValueError(f"{MRAF_SHAPES} (got {h} x {w})")
-        if not (np.isfinite(mixing) and 0 < mixing <= 1):
-            raise ValueError(f"mixing must be in (0, 1], got {mixing}")
+        _fused_only(_MRAF, h, w)
+        _check_mixing(mixing)
         if regions is None:
             raise ValueError("an MRAF sequence needs the signal regions of its frames")
         sr = np.asarray(regions) != 0
@@ -417,9 +429,7 @@ def _sequence_inputs(targets, loops_first, loops, algorithm, tol, ain, initial_p
             raise ValueError(f"regions of shape {np.asarray(regions).shape} do not match targets of shape "
                              f"{np.asarray(targets).shape}")
         for i in range(f):
-            for k in range(b):
-                if not np.any(sr[i, k] & (tdev[i, k] > 0)):
-                    raise ValueError(f"frame {i}: the signal region of hologram {k} holds no pixel with T > 0")
+            _check_support(sr[i], tdev[i], f"frame {i}: ")
     elif regions is not None:
         raise ValueError("regions apply to algorithm 'mraf' only")
     if ain is not None and np.asarray(ain).shape != (h, w):
@@ -461,20 +471,16 @@ def run_sequence(targets, loops_first, loops, algorithm="gerchberg_saxton", tol=
     plan.sequence(tdev, sr, loops_first=loops_first, loops=loops, tol=tol, mask=mask, ct2pi=ct2pi, rule=rule,
                   frames=True, phases=True, expected=return_expected)
     frames, phases, e, stats, _, iters = plan.sequence_read(frames=True, phases=True, expected=return_expected)
-    errs, maxes = [], np.empty((f, b), np.float64)
+    errs, maxes = [], []
     for i in range(f):
-        errs.append([])
-        for k in range(b):
-            n = loops_first if i == 0 else loops
-            if tol > 0 and iters[i, k] >= 0:
-                n = int(iters[i, k])
-            errs[i].append([np.float64(v) for v in stats[i, k, :n, 3]])
-            maxes[i, k] = stats[i, k, n - 1, 0]
+        frame_errs, frame_maxes = _errors(stats[i], iters[i], loops if i else loops_first, tol > 0)
+        errs.append(frame_errs)
+        maxes.append(frame_maxes)
     if sr is None:
         norm = tdev.reshape(f, b, -1).max(axis=2).astype(np.float64)
     else:
         norm = np.where(sr, tdev, 0).reshape(f, b, -1).max(axis=2).astype(np.float64)
-    out = phases, frames, errs, norm, maxes
+    out = phases, frames, errs, norm, np.array(maxes)
     return out + (e,) if return_expected else out
 
 
@@ -496,25 +502,11 @@ def run_gs_multi(targets, loops, devices, tol=0.0, ain=None, feedback=None):
         return run_gs(t, loops, tol, ain) if feedback is None else run_gsw(t, loops, feedback, tol, ain)
     tdev, _ = target_for_device(t)
     if feedback is not None:
-        _check_gsw_shape(*tdev.shape[1:])
+        _fused_only(_GSW, *tdev.shape[1:])
     phase, e, stats, iters = _lib.gs_multi(tdev, loops, devices, tol=tol, ain=ain, feedback=feedback)
     norm = t.reshape(t.shape[0], -1).max(axis=1).astype(np.float64)  # np.amax(demanded_output)
-    errs, maxes = [], []
-    for k in range(t.shape[0]):
-        n = loops if iters[k] < 0 else int(iters[k])
-        errs.append([np.float64(v) for v in stats[k, :n, 3]])
-        maxes.append(stats[k, n - 1, 0])
-    return phase, e, errs, norm, np.array(maxes)
-
-
-def _collect(plan, phase, e, stats, iters, loops, checked):
-    norm, _ = plan.target_stats()
-    errs, maxes = [], []
-    for k in range(plan.batch):
-        n = loops if (not checked or iters[k] < 0) else int(iters[k])
-        errs.append([np.float64(v) for v in stats[k, :n, 3]])
-        maxes.append(stats[k, n - 1, 0])
-    return phase, e, errs, norm, np.array(maxes)
+    errs, maxes = _errors(stats, iters, loops, True)  # the shards' iters count at every tolerance
+    return phase, e, errs, norm, maxes
 
 
 def run_gd(targets, loops, rates, white_attention, tol=0.0, ain=None, initial_field=None, return_field=False):
@@ -528,15 +520,7 @@ def run_gd(targets, loops, rates, white_attention, tol=0.0, ain=None, initial_fi
         plan.set_ain(ain)
     plan.set_field(initial_field)
     plan.set_lr(np.asarray(rates, np.float32)[:loops])
-    checked = tol > 0
-    plan.run(loops, tol, checked, white_attention)
-    phase, e, stats, iters = plan.read()
-    if not checked:
-        if any(_stop_index(stats[k, :loops, 3], tol) not in (None, loops - 1) for k in range(b)):
-            plan.run(loops, tol, True, white_attention)
-            phase, e, stats, iters = plan.read()
-            checked = True
-    out = _collect(plan, phase, e, stats, iters, loops, checked)
+    out = _collect(plan, loops, _run(plan, loops, tol, white_attention))
     return out + (plan.read_field(),) if return_field else out
 
 
@@ -580,6 +564,54 @@ def _iterations_allowed(args):
     return args.max_loops > 0 and (tol + 1) > tol
 
 
+def _no_iterations(args, variable):
+    """Where the reference's loop body never runs, its report and its failure
+    on `variable`, which only the body assigns."""
+    if _iterations_allowed(args):
+        return
+    print()
+    if args.print_info:
+        print()
+        printout(args.tolerance + 1, 0, [], args.plot_error)
+    raise UnboundLocalError(f"local variable '{variable}' referenced before assignment")
+
+
+def _chunks(args, chunk, kind="gs"):
+    """The iterations of an entry point: (phase, expected outcome, errors).
+    chunk(n, at, last) runs n iterations from iteration `at` and returns its
+    run_*'s result; `last` is the result of the chunk before, which holds the
+    state to continue from, or None at the start. A plain run is one chunk. GIF
+    frames need intermediate states: a GIF run goes in warm-started chunks
+    that end on every frame iteration."""
+    loops, tol = args.max_loops, args.tolerance
+    error_evolution, out, i = [], None, 0
+    while i < loops:
+        if not args.gif:
+            n = loops
+        else:
+            n = 1 if i % args.gif_skip == 0 else min(args.gif_skip - i % args.gif_skip, loops - i)
+        out = chunk(n, i, out)
+        phase, e, errs, norm, emax = out[:5]
+        error_evolution += errs[0]
+        i += len(errs[0])
+        expected = expected_from(e[0], norm[0], emax[0])
+        if args.gif and (i - 1) % args.gif_skip == 0:
+            _gif_frame(args, kind, (out[5] if kind == "gd" else phase)[0], expected, i - 1)
+        if len(errs[0]) < n or not (error_evolution[-1] > tol):
+            break
+    return phase, expected, error_evolution
+
+
+def _report(args, phase, expected, error_evolution):
+    """The reference's lines after its loop, and its return triple."""
+    n = len(error_evolution)
+    _print_loops(n, args.max_loops)
+    if args.print_info:
+        print()
+        printout(error_evolution[-1], n, error_evolution, args.plot_error)
+    return hologram_from(phase[0]), expected, error_evolution
+
+
 def _gif_frame(args, kind, phase, expected, i):
     """add_gif_image (src/algorithms.py:52-57) for GS; the GD frame of
     src/algorithms.py:94-101 (complex_to_real_phase of x/|x|, :175-176) when
@@ -604,27 +636,15 @@ def gerchberg_saxton(demanded_output, args):
     """Classical Gerchberg-Saxton (far field) on the GPU; drop-in for
     src/algorithms.py:10-49."""
     t = np.asarray(demanded_output)
-    h, w = _check_shape(t)
+    _check_shape(t)
     ain = incoming_amplitude(args, t.shape)
     tol = args.tolerance
-    if not _iterations_allowed(args):
-        print()
-        if args.print_info:
-            print()
-            printout(tol + 1, 0, [], args.plot_error)
-        raise UnboundLocalError("local variable 'expected_outcome' referenced before assignment")
-    if args.gif:
-        return _gerchberg_saxton_gif(t, args, ain)
-    phase, e, errs, norm, emax = run_gs(t[None], args.max_loops, tol, ain)
-    error_evolution = errs[0]
-    n = len(error_evolution)
-    _print_loops(n, args.max_loops)
-    if args.print_info:
-        print()
-        printout(error_evolution[-1], n, error_evolution, args.plot_error)
-    hologram = hologram_from(phase[0])
-    expected_outcome = expected_from(e[0], norm[0], emax[0])
-    return hologram, expected_outcome, error_evolution
+    _no_iterations(args, "expected_outcome")
+
+    def chunk(n, at, last):  # the GS state is angle(A) only
+        return run_gs(t[None], n, tol, ain, initial_phase=None if last is None else last[0])
+
+    return _report(args, *_chunks(args, chunk))
 
 
 def weighted_gerchberg_saxton(demanded_output, args):
@@ -635,26 +655,17 @@ def weighted_gerchberg_saxton(demanded_output, args):
     gerchberg_saxton's. Reads ``args.feedback`` (the exponent p, default 1)."""
     t = np.asarray(demanded_output)
     h, w = _check_shape(t)
-    _check_gsw_shape(h, w)
+    _fused_only(_GSW, h, w)
     feedback = float(getattr(args, "feedback", 1.0))
     ain = incoming_amplitude(args, t.shape)
     tol = args.tolerance
-    if not _iterations_allowed(args):
-        print()
-        if args.print_info:
-            print()
-            printout(tol + 1, 0, [], args.plot_error)
-        raise UnboundLocalError("local variable 'expected_outcome' referenced before assignment")
-    if args.gif:
-        return _gerchberg_saxton_gif(t, args, ain, feedback)
-    phase, e, errs, norm, emax = run_gsw(t[None], args.max_loops, feedback, tol, ain)
-    error_evolution = errs[0]
-    n = len(error_evolution)
-    _print_loops(n, args.max_loops)
-    if args.print_info:
-        print()
-        printout(error_evolution[-1], n, error_evolution, args.plot_error)
-    return hologram_from(phase[0]), expected_from(e[0], norm[0], emax[0]), error_evolution
+    _no_iterations(args, "expected_outcome")
+
+    def chunk(n, at, last):  # a GIF run hands the weights on as well as the phase
+        phase, weights = (None, None) if last is None else (last[0], last[5])
+        return run_gsw(t[None], n, feedback, tol, ain, phase, weights, return_weights=args.gif)
+
+    return _report(args, *_chunks(args, chunk))
 
 
 def mraf(demanded_output, args):
@@ -678,118 +689,38 @@ def mraf(demanded_output, args):
         raise ValueError(f"signal region of shape {region.shape} does not match the target's {t.shape}")
     ain = incoming_amplitude(args, t.shape)
     tol = args.tolerance
-    if not _iterations_allowed(args):
-        print()
-        if args.print_info:
-            print()
-            printout(tol + 1, 0, [], args.plot_error)
-        raise UnboundLocalError("local variable 'expected_outcome' referenced before assignment")
-    if args.gif:
-        return _gerchberg_saxton_gif(t, args, ain, mraf=(region[None], mixing))
-    phase, e, errs, norm, emax = run_mraf(t[None], region[None], args.max_loops, mixing, tol, ain)
-    error_evolution = errs[0]
-    n = len(error_evolution)
-    _print_loops(n, args.max_loops)
-    if args.print_info:
-        print()
-        printout(error_evolution[-1], n, error_evolution, args.plot_error)
-    return hologram_from(phase[0]), expected_from(e[0], norm[0], emax[0]), error_evolution
+    _no_iterations(args, "expected_outcome")
 
+    def chunk(n, at, last):  # the MRAF state is angle(A) only, as GS's
+        return run_mraf(t[None], region[None], n, mixing, tol, ain, initial_phase=None if last is None else last[0])
 
-def _gerchberg_saxton_gif(t, args, ain, feedback=None, mraf=None):
-    """GIF frames need intermediate states: run in warm-started chunks that end
-    on every frame iteration (the GS state is angle(A) only; weighted GS, with
-    a feedback exponent given, also hands its weights from chunk to chunk)."""
-    loops, tol, skip = args.max_loops, args.tolerance, args.gif_skip
-    phase = None
-    weights = None
-    error_evolution = []
-    i = 0
-    while i < loops:
-        step = 1 if i % skip == 0 else min(skip - i % skip, loops - i)
-        if mraf is not None:  # the MRAF state is angle(A) only, as GS's
-            ph, e, errs, norm, emax = run_mraf(t[None], mraf[0], step, mraf[1], tol, ain, initial_phase=phase)
-        elif feedback is None:
-            ph, e, errs, norm, emax = run_gs(t[None], step, tol, ain, initial_phase=phase)
-        else:
-            ph, e, errs, norm, emax, weights = run_gsw(t[None], step, feedback, tol, ain, initial_phase=phase,
-                                                        initial_weights=weights, return_weights=True)
-        error_evolution += errs[0]
-        phase = ph
-        i += len(errs[0])
-        expected = expected_from(e[0], norm[0], emax[0])
-        if (i - 1) % skip == 0:
-            _gif_frame(args, "gs", ph[0], expected, i - 1)
-        if len(errs[0]) < step or not (error_evolution[-1] > tol):
-            break
-    _print_loops(len(error_evolution), loops)
-    if args.print_info:
-        print()
-        printout(error_evolution[-1], len(error_evolution), error_evolution, args.plot_error)
-    return hologram_from(phase[0]), expected, error_evolution
+    return _report(args, *_chunks(args, chunk))
 
 
 def gradient_descent(demanded_output, args):
     """Gradient descent on the unconstrained complex field (far field) on the
     GPU; drop-in for src/algorithms.py:60-112."""
     t = np.asarray(demanded_output)
-    h, w = _check_shape(t)
+    _check_shape(t)
     ain = incoming_amplitude(args, t.shape)
     amp_host = np.ones(t.shape) if ain is None else ain.astype(np.float64)
     field = make_initial_guess(args.initial_guess, amp_host, t, args.random_seed)
     tol = args.tolerance
     if args.print_info:
         print("computing hologram")
-    if not _iterations_allowed(args):
-        print()
-        if args.print_info:
-            print()
-            printout(tol + 1, 0, [], args.plot_error)
-        raise UnboundLocalError("local variable 'output' referenced before assignment")
+    _no_iterations(args, "output")
     if args.unsettle and int(round(args.max_loops / (args.unsettle + 1))) == 0:
         raise ZeroDivisionError("integer division or modulo by zero")
     rates, after = learning_rates(args.learning_rate, args.max_loops, args.unsettle)
-    if args.gif:
-        return _gradient_descent_gif(t, args, ain, field, rates, after)
-    phase, e, errs, norm, emax = run_gd(t[None], args.max_loops, rates, float(args.white_attention), tol, ain,
-                                        None if field is None else field[None])
-    error_evolution = errs[0]
-    n = len(error_evolution)
-    args.learning_rate = float(after[n]) if args.unsettle else args.learning_rate
-    _print_loops(n, args.max_loops)
-    if args.print_info:
-        print()
-        printout(error_evolution[-1], n, error_evolution, args.plot_error)
-    hologram = hologram_from(phase[0])
-    output = expected_from(e[0], norm[0], emax[0])
-    return hologram, output, error_evolution
+    x0 = None if field is None else field[None]
 
+    def chunk(n, at, last):
+        """The GD state is the complex field x, read back after each chunk of a
+        GIF run (slm_plan_read_field) and handed to the next with the matching
+        slice of the learning-rate schedule."""
+        return run_gd(t[None], n, rates[at:at + n], float(args.white_attention), tol, ain,
+                      x0 if last is None else last[5], return_field=args.gif)
 
-def _gradient_descent_gif(t, args, ain, field, rates, after):
-    """GD with GIF frames (src/algorithms.py:94-101): warm-started chunks that
-    end on every frame iteration; the GD state is the complex field x, read
-    back after each chunk (slm_plan_read_field) and handed to the next with the
-    matching slice of the learning-rate schedule."""
-    loops, tol, skip = args.max_loops, args.tolerance, args.gif_skip
-    error_evolution = []
-    i = 0
-    x = None if field is None else field[None]
-    while i < loops:
-        step = 1 if i % skip == 0 else min(skip - i % skip, loops - i)
-        ph, e, errs, norm, emax, xf = run_gd(t[None], step, rates[i:i + step], float(args.white_attention), tol,
-                                             ain, x, return_field=True)
-        x = xf
-        error_evolution += errs[0]
-        i += len(errs[0])
-        output = expected_from(e[0], norm[0], emax[0])
-        if (i - 1) % skip == 0:
-            _gif_frame(args, "gd", xf[0], output, i - 1)
-        if len(errs[0]) < step or not (error_evolution[-1] > tol):
-            break
-    n = len(error_evolution)
-    args.learning_rate = float(after[n]) if args.unsettle else args.learning_rate
-    _print_loops(n, loops)
-    if args.print_info:
-        print()
-        printout(error_evolution[-1], n, error_evolution, args.plot_error)
-    return hologram_from(ph[0]), output, error_evolution
+    phase, output, error_evolution = _chunks(args, chunk, "gd")
+    args.learning_rate = float(after[len(error_evolution)]) if args.unsettle else args.learning_rate
+    return _report(args, phase, output, error_evolution)

@@ -24,8 +24,8 @@ import numpy as np
 
 from . import parallel
 from . import _lib
-from .algorithms import (_check_shape, _print_loops, expected_from, hologram_from, incoming_amplitude, run_gs,
-                         run_gs_multi, run_gsw, run_sequence)
+from .algorithms import (_check_shape, _iterations_allowed, _print_loops, expected_from, hologram_from,
+                         incoming_amplitude, run_gs, run_gs_multi, run_gsw, run_sequence)
 
 SEQ_BATCH = int(os.environ.get("SLM_SEQ_BATCH", "64"))  # frames per GPU launch batch
 SEQ_CHAIN = int(os.environ.get("SLM_SEQ_CHAIN", "256"))  # frames per enqueued chain (--chain)
@@ -37,47 +37,64 @@ def _load_frame(source_dir_path, i):
     return np.array(Image.open(f"{source_dir_path}/{i}.png"))
 
 
-def _batches(indices, frames):
-    """Split an index list into runs of equal shape and dtype, at most SEQ_BATCH long."""
+def _runs(indices, frames, ends):
+    """Split an index list into runs of equal shape and dtype; ends(run, i)
+    tells whether frame i may not join `run` for another reason."""
     run = []
     for i in indices:
-        if run and (len(run) == SEQ_BATCH or frames[i].shape != frames[run[0]].shape
+        if run and (ends(run, i) or frames[i].shape != frames[run[0]].shape
                     or frames[i].dtype != frames[run[0]].dtype):
             yield run
             run = []
         run.append(i)
     if run:
         yield run
+
+
+def _batches(indices, frames):
+    """Split an index list into runs of equal shape and dtype, at most SEQ_BATCH long."""
+    return _runs(indices, frames, lambda run, i: len(run) == SEQ_BATCH)
 
 
 def _chains(indices, frames):
     """Split an index list into runs of consecutive frames of equal shape and dtype."""
-    run = []
-    for i in indices:
-        if run and (i != run[-1] + 1 or frames[i].shape != frames[run[0]].shape
-                    or frames[i].dtype != frames[run[0]].dtype):
-            yield run
-            run = []
-        run.append(i)
-    if run:
-        yield run
+    return _runs(indices, frames, lambda run, i: i != run[-1] + 1)
 
 
-def _chained(args, mine, frames, dest_dir_holograms, dest_dir_preview):
+def _ain_for(args, frame):
+    """What gerchberg_saxton does before its loop, for the frames of frame's shape."""
+    _check_shape(frame)
+    ain = incoming_amplitude(args, frame.shape)
+    if not _iterations_allowed(args):
+        raise UnboundLocalError("local variable 'expected_outcome' referenced before assignment")
+    return ain
+
+
+def _write_frames(args, dest_dirs, idx, phase, e, errs, norm, emax):
+    """The reference's lines and files for frames idx, from run_gs's result
+    for them; returns their error evolutions."""
+    from PIL import Image
+
+    for k, i in enumerate(idx):
+        sys.stdout.write(f"\rcreating {i}. hologram ")
+        _print_loops(len(errs[k]), args.max_loops)
+        np.save(f"{dest_dirs[0]}/{i}.npy", hologram_from(phase[k]))
+        if args.preview:
+            expected = expected_from(e[k], norm[k], emax[k])
+            Image.fromarray(expected).convert("L").save(f"{dest_dirs[1]}/{i}.png")
+    return dict(zip(idx, errs))
+
+
+def _chained(args, mine, frames, dest_dirs):
     """--chain: this rank's frames as device-resident chains (run_sequence):
     every frame after the first of a run starts from the phase of the frame
     before it. A run longer than SEQ_CHAIN goes in pieces, each continued from
     the last phase of the piece before it, which is the uncut chain."""
-    from PIL import Image
-
     algorithm = getattr(args, "algorithm", "gerchberg_saxton")
     feedback = float(getattr(args, "feedback", 1.0))
     errors = {}
     for run in _chains(mine, frames):
-        _check_shape(frames[run[0]])
-        ain = incoming_amplitude(args, frames[run[0]].shape)
-        if not (args.max_loops > 0 and (args.tolerance + 1) > args.tolerance):
-            raise UnboundLocalError("local variable 'expected_outcome' referenced before assignment")
+        ain = _ain_for(args, frames[run[0]])
         last = None
         for at in range(0, len(run), SEQ_CHAIN):
             idx = run[at:at + SEQ_CHAIN]
@@ -85,14 +102,9 @@ def _chained(args, mine, frames, dest_dir_holograms, dest_dir_preview):
             phase, _, errs, norm, emax, e = run_sequence(stack, args.max_loops, args.max_loops, algorithm,
                                                          args.tolerance, ain, last, feedback, return_expected=True)
             last = phase[-1]
-            for k, i in enumerate(idx):
-                sys.stdout.write(f"\rcreating {i}. hologram ")
-                _print_loops(len(errs[k][0]), args.max_loops)
-                errors[i] = errs[k][0]
-                np.save(f"{dest_dir_holograms}/{i}.npy", hologram_from(phase[k, 0]))
-                if args.preview:
-                    expected = expected_from(e[k, 0], norm[k, 0], emax[k, 0])
-                    Image.fromarray(expected).convert("L").save(f"{dest_dir_preview}/{i}.png")
+            # a frame of the chain is a batch of one hologram
+            errors.update(_write_frames(args, dest_dirs, idx, phase[:, 0], e[:, 0], [x[0] for x in errs],
+                                        norm[:, 0], emax[:, 0]))
     return errors
 
 
@@ -111,13 +123,11 @@ def multi_devices(nranks):
 def generate_hologram_sequence(args, rank=None, nranks=None):
     """src/generate_hologram_sequence.py:10-31. Returns the per-frame error
     evolutions of the frames this rank computed (dict frame -> list)."""
-    from PIL import Image
-
     if rank is None:
         rank, nranks, _ = parallel.world()
-    dest_dir_holograms = f"holograms/{args.source_dir}_{args.version}_holograms"
-    dest_dir_preview = f"images/moving_traps/{args.source_dir}_{args.version}_preview"
-    for dest_dir in (dest_dir_holograms, dest_dir_preview):
+    dest_dirs = (f"holograms/{args.source_dir}_{args.version}_holograms",
+                 f"images/moving_traps/{args.source_dir}_{args.version}_preview")
+    for dest_dir in dest_dirs:
         os.makedirs(dest_dir, exist_ok=True)
     source_dir_path = f"images/moving_traps/{args.source_dir}"
     n_files = len(os.listdir(source_dir_path))
@@ -125,31 +135,21 @@ def generate_hologram_sequence(args, rank=None, nranks=None):
     frames = {i: _load_frame(source_dir_path, i) for i in mine}
     errors = {}
     if getattr(args, "chain", False):
-        return _chained(args, mine, frames, dest_dir_holograms, dest_dir_preview)
+        return _chained(args, mine, frames, dest_dirs)
     devices = multi_devices(nranks)
     for idx in _batches(mine, frames):
         stack = np.stack([frames[i] for i in idx])
-        _check_shape(stack[0])
-        ain = incoming_amplitude(args, stack.shape[1:])
-        if not (args.max_loops > 0 and (args.tolerance + 1) > args.tolerance):
-            raise UnboundLocalError("local variable 'expected_outcome' referenced before assignment")
+        ain = _ain_for(args, stack[0])
         # -alg weighted_gerchberg_saxton (no reference counterpart): the same batches, weighted GS
         feedback = (float(getattr(args, "feedback", 1.0))
                     if getattr(args, "algorithm", "gerchberg_saxton") == "weighted_gerchberg_saxton" else None)
         if devices:
-            phase, e, errs, norm, emax = run_gs_multi(stack, args.max_loops, devices, args.tolerance, ain, feedback)
+            result = run_gs_multi(stack, args.max_loops, devices, args.tolerance, ain, feedback)
         elif feedback is not None:
-            phase, e, errs, norm, emax = run_gsw(stack, args.max_loops, feedback, args.tolerance, ain)
+            result = run_gsw(stack, args.max_loops, feedback, args.tolerance, ain)
         else:
-            phase, e, errs, norm, emax = run_gs(stack, args.max_loops, args.tolerance, ain)
-        for k, i in enumerate(idx):
-            sys.stdout.write(f"\rcreating {i}. hologram ")
-            _print_loops(len(errs[k]), args.max_loops)
-            errors[i] = errs[k]
-            np.save(f"{dest_dir_holograms}/{i}.npy", hologram_from(phase[k]))
-            if args.preview:
-                expected = expected_from(e[k], norm[k], emax[k])
-                Image.fromarray(expected).convert("L").save(f"{dest_dir_preview}/{i}.png")
+            result = run_gs(stack, args.max_loops, args.tolerance, ain)
+        errors.update(_write_frames(args, dest_dirs, idx, *result))
     return errors
 
 
