@@ -23,6 +23,9 @@
  *   slm_spots_*                           -> no reference counterpart: weighted GS on a list
  *                                            of traps (fractional positions, defocus, any
  *                                            panel shape; see "trap lists" below).
+ *   slm_farfield_zoom                     -> no reference counterpart: the far field of any
+ *                                            hologram or SLM frame on a fractional grid (see
+ *                                            "zoomed far field" below).
  *   slm_comm_* / slm_plan_gather_phase    -> no reference counterpart: the batch
  *                                            loop of src/generate_hologram_sequence.py:19-31
  *                                            sharded over GPUs, phases gathered over RCCL.
@@ -533,6 +536,56 @@ int slm_spots_fields(int batch, int height, int width, int n_traps, const double
                      const double* zs, const float* ain, const float* phase, double* fields_out);
 int slm_spots_superpose(int batch, int height, int width, int n_traps, const double* ys, const double* xs,
                         const double* zs, const double* c_re_im, float* phase_out);
+
+/* ---- zoomed far field: no reference counterpart ---------------------------
+ * The far field of a hologram on a regular fractional grid, in the trap-list
+ * conventions above, so that a sample is what slm_spots_fields gives for a trap
+ * at its position. Per hologram of H x W pixels (row k, column l), a = a_in or
+ * ones, u = exp(i phi), a window of ny x nx samples y_j = y0 + j dy,
+ * x_i = x0 + i dx (far-field pixels = FFT bins, fractional, any sign; formed in
+ * float64) and one defocus z in radians per pixel^2 for the whole window:
+ *     fy_j(k) = 2 pi frac(k y_j / H) + z (k - H/2)^2      fx_i(l) likewise with x_i, W
+ *     R[k][i] = sum_l a(k,l) u(k,l) exp(-i fx_i(l))
+ *     V[j][i] = sum_k exp(-i fy_j(k)) R[k][i]
+ *     I[j][i] = |V[j][i]|^2
+ * For integer y0, x0, dy = dx = 1 and z = 0, V is fft2(a u)[y_j mod H][x_i mod W].
+ * `hologram` is [batch][h][w]: SLM_ZOOM_PHASE_F32, a float32 phase in radians
+ * (u = its float64 sine and cosine rounded to complex64, as slm_spots_set_phase
+ * forms it), or SLM_ZOOM_LEVELS_U8, a uint8 SLM frame as it is displayed
+ * (u = exp(i 2 pi level / ct2pi), evaluated in float64 per level and rounded to
+ * complex64; no correction mask is applied). ct2pi is read for levels only.
+ * Both sums are float32 matrix products on the matrix cores
+ * (v_mfma_f32_32x32x2_f32) with tables built as the trap lists' are; no float32
+ * chain is longer than 256 summed pixels, the chunks (pixels 256 c .. 256 c + 255)
+ * are added in float64 in their order (in registers, or from a partial buffer
+ * when the sum is split over workgroups: the same additions), R is rounded to
+ * complex64 once. No atomics: results are bitwise reproducible, do not depend
+ * on the batch, and a sample's value depends on its position alone, not on the
+ * window around it.
+ * slm_farfield_zoom: one-shot, host pointers in and out; the batch shares the
+ *   window and ain [h][w] (NULL = ones) and runs hologram by hologram;
+ *   intensity [batch][ny][nx] float32; field [batch][ny][nx][2] = V from the
+ *   float64 fold, or NULL. It synchronises and frees its buffers before it
+ *   returns. SLM_ERR_ARG: a null hologram or intensity, an unknown kind,
+ *   batch < 1, a side outside 2 .. 4096, ny or nx outside 1 .. 4096, y0, x0, dy,
+ *   dx or z not finite, dy or dx <= 0, ct2pi not finite or <= 0 with levels, a
+ *   non-finite a_in entry, a_in zero everywhere.
+ * slm_farfield_zoom_timed: the same; kernel_us[SLM_ZOOM_NUM_KERNEL_CLASSES]
+ *   (NULL = untimed) receives the microseconds HIP events measured around the
+ *   kernels of each class, summed over the holograms; copies are excluded.    */
+#define SLM_ZOOM_PHASE_F32 0
+#define SLM_ZOOM_LEVELS_U8 1
+#define SLM_ZOOM_KERNEL_TABLES 0 /* zoom_table_kernel: Px and Py, once per call */
+#define SLM_ZOOM_KERNEL_FIELD 1  /* zoom_field_kernel: a u as complex64 */
+#define SLM_ZOOM_KERNEL_ROWS 2   /* zoom_rows_kernel (and its fold when the columns are split): R */
+#define SLM_ZOOM_KERNEL_COLS 3   /* zoom_cols_kernel and zoom_fold_kernel: V and I */
+#define SLM_ZOOM_NUM_KERNEL_CLASSES 4
+int slm_farfield_zoom(const void* hologram, int kind, int batch, int height, int width, const float* ain, double ct2pi,
+                      double y0, double x0, double dy, double dx, int ny, int nx, double z, float* intensity,
+                      double* field);
+int slm_farfield_zoom_timed(const void* hologram, int kind, int batch, int height, int width, const float* ain,
+                            double ct2pi, double y0, double x0, double dy, double dx, int ny, int nx, double z,
+                            float* intensity, double* field, double* kernel_us);
 
 /* ---- CLI post-processing ------------------------------
  * slm_transform_hologram -> transform_hologram(hologram, args)

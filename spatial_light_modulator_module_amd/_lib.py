@@ -143,7 +143,22 @@ _SIGNATURES = [
     ("slm_spots_sequence_read", _c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("slm_spots_fields", _c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("slm_spots_superpose", _c_int, [_c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
+    ("slm_farfield_zoom", _c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_double, _c_double, _c_double,
+                                   _c_double, _c_double, _c_int, _c_int, _c_double, _vp, _vp]),
+    ("slm_farfield_zoom_timed", _c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_double, _c_double, _c_double,
+                                         _c_double, _c_double, _c_int, _c_int, _c_double, _vp, _vp, _vp]),
 ]
+
+ZOOM_PHASE_F32 = 0
+ZOOM_LEVELS_U8 = 1
+ZOOM_KERNEL_TABLES = 0
+ZOOM_KERNEL_FIELD = 1
+ZOOM_KERNEL_ROWS = 2
+ZOOM_KERNEL_COLS = 3
+ZOOM_NUM_KERNEL_CLASSES = 4
+ZOOM_KERNEL_CLASS_NAMES = ("tables", "field", "rows", "cols")
+ZOOM_MIN_SIDE, ZOOM_MAX_SIDE = 2, 4096  # hologram sides
+ZOOM_MAX_SAMPLES = 4096  # per window side
 
 SPOTS_KERNEL_FIELDS = 0
 SPOTS_KERNEL_UPDATE = 1
@@ -731,6 +746,83 @@ def spots_superpose(shape, c, ys, xs, zs=None) -> np.ndarray:
     check(load().slm_spots_superpose(b, h, w, n, ptr(y), ptr(x), ptr(z), cc.ctypes.data, ptr(out)),
           "slm_spots_superpose")
     return out
+
+
+def _pair(v, name, kind=float):
+    """(a, b) from a pair, or from one number for both axes."""
+    p = tuple(np.ravel(v).tolist())
+    if len(p) == 1:
+        p = p * 2
+    if len(p) != 2:
+        raise ValueError(f"{name} is one number or a (y, x) pair, got {v!r}")
+    if kind is int:
+        if any(int(c) != c for c in p):
+            raise ValueError(f"{name} must be whole numbers, got {v!r}")
+        return int(p[0]), int(p[1])
+    return float(p[0]), float(p[1])
+
+
+def farfield_zoom(hologram, origin, pitch, size, z=0.0, ain=None, ct2pi=None, return_field=False, timed=False):
+    """slm_farfield_zoom: the far field of a hologram on the ny x nx samples
+    y_j = origin[0] + j pitch[0], x_i = origin[1] + i pitch[1] (far-field
+    pixels, fractional; `pitch` may be one number for both axes) with one
+    defocus z (radians per pixel^2), in the trap-list conventions: a sample is
+    what spots_fields gives for a trap there. `hologram` is [H][W] or
+    [B][H][W]: a floating dtype is a phase in radians (taken as float32), uint8
+    an SLM frame whose levels mean exp(i 2 pi level / ct2pi) (ct2pi required;
+    no correction mask is applied). ain [H][W] is shared by the batch. Returns
+    the float32 intensity |V|^2 in the hologram's leading shape + (ny, nx);
+    with return_field also V complex128; with timed also the microseconds per
+    kernel class (ZOOM_KERNEL_*) HIP events measured. Every argument is checked here
+    (ValueError) before the device is touched."""
+    holo = np.asarray(hologram)
+    if holo.ndim not in (2, 3):
+        raise ValueError(f"a hologram is [H][W] or [B][H][W], got shape {holo.shape}")
+    if holo.dtype == np.uint8:
+        kind = ZOOM_LEVELS_U8
+        if ct2pi is None or not np.isfinite(ct2pi) or not ct2pi > 0:
+            raise ValueError(f"a uint8 frame needs ct2pi finite and positive, got {ct2pi!r}")
+    elif np.issubdtype(holo.dtype, np.floating):
+        kind = ZOOM_PHASE_F32
+        holo = holo.astype(np.float32, copy=False)
+    else:
+        raise ValueError(f"a hologram is a floating phase or a uint8 frame, got dtype {holo.dtype}")
+    single = holo.ndim == 2
+    holo = np.ascontiguousarray(holo[None] if single else holo)
+    b, h, w = holo.shape
+    if b < 1:
+        raise ValueError("the batch holds no hologram")
+    if not (ZOOM_MIN_SIDE <= h <= ZOOM_MAX_SIDE and ZOOM_MIN_SIDE <= w <= ZOOM_MAX_SIDE):
+        raise ValueError(f"the zoom runs on sides {ZOOM_MIN_SIDE} .. {ZOOM_MAX_SIDE}, got {h} x {w}")
+    (y0, x0), (dy, dx), (ny, nx) = _pair(origin, "origin"), _pair(pitch, "pitch"), _pair(size, "size", int)
+    if not (1 <= ny <= ZOOM_MAX_SAMPLES and 1 <= nx <= ZOOM_MAX_SAMPLES):
+        raise ValueError(f"a window has 1 .. {ZOOM_MAX_SAMPLES} samples per side, got {ny} x {nx}")
+    if not all(np.isfinite(v) for v in (y0, x0, dy, dx, float(z))):
+        raise ValueError("the window's origin, pitch and defocus must be finite")
+    if not (dy > 0 and dx > 0):
+        raise ValueError(f"the pitch must be positive, got {dy} x {dx}")
+    a = None
+    if ain is not None:
+        a = np.ascontiguousarray(ain, dtype=np.float32)
+        if a.shape != (h, w):
+            raise ValueError(f"ain has shape {a.shape}, the hologram {(h, w)}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError("ain has a non-finite entry")
+        if not np.any(a):
+            raise ValueError("ain is zero everywhere")
+    out = np.empty((b, ny, nx), np.float32)
+    field = np.empty((b, ny, nx), np.complex128) if return_field else None
+    us = np.zeros(ZOOM_NUM_KERNEL_CLASSES, np.float64) if timed else None
+    init()
+    check(load().slm_farfield_zoom_timed(ptr(holo), kind, b, h, w, ptr(a), float(ct2pi or 0.0), y0, x0, dy, dx, ny, nx,
+                                         float(z), ptr(out), None if field is None else field.ctypes.data, ptr(us)),
+          "slm_farfield_zoom")
+    res = [out[0] if single else out]
+    if return_field:
+        res.append(field[0] if single else field)
+    if timed:
+        res.append(us)
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 def fft2(x: np.ndarray, inverse: bool = False) -> np.ndarray:

@@ -56,40 +56,19 @@
 
 #include "quantize.hpp"
 #include "runtime.hpp"
+#include "spot_tiles.hpp"  // the tile constants, acc_row, mfma and table_entry (shared with zoom.hip)
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace slm::tiles;
 
-constexpr double kTwoPi = 6.283185307179586;
 constexpr double kGolden = 0.6180339887498949;
-constexpr int kTile = 32;         // MFMA tile side
-constexpr int kLdsStride = 66;    // floats per staged field row (64 + 2: conflict-free 8 B reads)
 constexpr int kUpdThreads = 1024; // spot_update_kernel: one trap per thread after the fold
 constexpr int kMaxTraps = 1024;
-constexpr int kMinSide = 2, kMaxSide = 4096;
-constexpr int kWaves = 4;           // waves per workgroup of the two product kernels
 constexpr int kFieldsThreads = 64 * kWaves;
 constexpr int kTargetWaves = 4096;  // fields grid: split columns until this many waves per hologram
 
-// row of accumulator register r of a 32x32 MFMA result in lane half h (the column is lane & 31)
-__device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-__device__ __forceinline__ f32x16 mfma(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
 // ---- tables ---------------------------------------------------------------
-// one table entry: float64 with the argument reduced first, rounded to complex64
-__device__ __forceinline__ float2 table_entry(int n, int N, double pos, double z) {
-    double t = (double)n * pos / (double)N;
-    t -= floor(t);  // the argument of the sine is reduced to [0, 2 pi) first
-    const double d = (double)n - 0.5 * (double)N;
-    double s, c;
-    sincos(kTwoPi * t + z * d * d, &s, &c);
-    return make_float2((float)c, (float)s);
-}
-
 // All four tables of one list (a handle's, or one frame's of a trajectory) in
 // one launch, from coordinates that are already on the device: elements
 // [0, H Mp) are Py, then PyT, Px and PxT, each stored along its own fast index.

@@ -3,6 +3,7 @@ of traps at fractional positions, one chain on the device per trajectory.
 
     python -m spatial_light_modulator_module_amd.generate_trap_sequence <name> -v V -ct2pi N [-loops 4] [-first 30]
         [-tol 0] [--feedback 1] [--shape 1080x1920] [-ii PATH] [-p]
+        [--expected [--oversample 8] [--margin 4] [--expected_z 0]]
 
 The reference reaches moving traps in two steps: generate_traps_image_sequence.py
 rasterises the positions into images (whole pixels), generate_hologram_sequence.py
@@ -17,7 +18,13 @@ is <= ``-tol``.
 Output is the layout generate_hologram_sequence writes, so display_holograms
 plays it: ``holograms/<name>_<V>_holograms/<i>.npy`` (float64, hologram_from);
 with ``-p`` also the quantised SLM frames as
-``images/moving_traps/<name>_<V>_preview/<i>.png``. Single GPU only.
+``images/moving_traps/<name>_<V>_preview/<i>.png``. With ``--expected`` the far
+field those uint8 frames produce is written too, as
+``images/moving_traps/<name>_<V>_expected/<i>.png``: one window for the whole
+trajectory (move_traps.trap_window: every position +- ``--margin`` far-field
+pixels, ``--oversample`` samples per pixel, in the plane of ``--expected_z``),
+all frames through one move_traps.expected_outcome call, each image scaled to
+its own brightest sample. Single GPU only.
 """
 from __future__ import annotations
 
@@ -57,6 +64,11 @@ def output_dirs(name, version):
     return f"holograms/{name}_{version}_holograms", f"images/moving_traps/{name}_{version}_preview"
 
 
+def expected_dir(name, version):
+    """Where --expected writes the zoomed far field of every frame."""
+    return f"images/moving_traps/{name}_{version}_expected"
+
+
 def generate_trap_sequence(args):
     """Runs the trajectory and writes its files; returns the per-frame
     uniformity curves (list of F lists, one value per executed iteration)."""
@@ -78,7 +90,25 @@ def generate_trap_sequence(args):
 
             Image.fromarray(res.frames[i]).save(f"{dest_preview}/{i}.png")
         curves.append([float(u) for u in res.stats[i][:int(res.iters[i]), 1]])
+    if args.expected:
+        write_expected(args, res.frames, ys, xs, ain)
     return curves
+
+
+def write_expected(args, frames, ys, xs, ain):
+    """--expected: what the uint8 frames produce, one zoomed far field for all
+    of them on the window of the whole trajectory, each written as an 8-bit
+    image scaled to its own brightest sample."""
+    from PIL import Image
+
+    dest = expected_dir(args.name, args.version)
+    os.makedirs(dest, exist_ok=True)
+    window = move_traps.trap_window(ys, xs, margin=args.margin, oversample=args.oversample)
+    inten = move_traps.expected_outcome(np.ascontiguousarray(frames), window, z=args.expected_z, ain=ain,
+                                        ct2pi=args.correspond_to2pi)
+    for i, img in enumerate(inten.astype(np.float64)):
+        peak = img.max() or 1.0  # a dark frame stays dark
+        Image.fromarray(np.floor(255.0 * img / peak).astype(np.uint8)).save(f"{dest}/{i}.png")  # uint8 2-D: mode L
 
 
 def build_parser():
@@ -101,6 +131,14 @@ def build_parser():
     p.add_argument("-ii", "--incomming_intensity", metavar="PATH", type=str, default="uniform",
                    help="incomming intensity image or 'uniform'")
     p.add_argument("-p", "--preview", action="store_true", help="also write the quantised frames as images")
+    p.add_argument("--expected", action="store_true",
+                   help="also write the far field each quantised frame produces around the traps, as images")
+    p.add_argument("--oversample", metavar="INT", default=8, type=int,
+                   help="--expected: samples per far-field pixel")
+    p.add_argument("--margin", metavar="PX", default=4.0, type=float,
+                   help="--expected: far-field pixels shown around the outermost trap positions")
+    p.add_argument("--expected_z", metavar="Z", default=0.0, type=float,
+                   help="--expected: defocus of the previewed plane, radians per pixel^2")
     return p
 
 

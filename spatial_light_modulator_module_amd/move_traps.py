@@ -23,6 +23,11 @@ DESIGN.md section 7).
   and leaves the device as the uint8 SLM frame. The reference's route to moving
   traps (generate_traps_image_sequence.py, then GS per rasterised frame) rounds
   the positions to whole pixels; this one keeps them fractional.
+* ``trap_window`` / ``expected_outcome`` — no reference counterpart: the far
+  field a hologram, or the uint8 frame sent to the panel, produces around a set
+  of trap positions, sampled between the FFT bins in a chosen focal plane
+  (slm_farfield_zoom). What show_expected_outcome's |fft2|^2 cannot show of a
+  trap at a fractional position.
 """
 from __future__ import annotations
 
@@ -250,6 +255,45 @@ def trap_array_sequence(shape, ys, xs, zs=None, intensity=None, loops_first=30, 
         return SequenceResult(frames[:, 0], None if holo is None else holo[:, 0], inten_out[:, 0], stats[:, 0],
                               iters[:, 0], weights[:, 0])
     return SequenceResult(frames, holo, inten_out, stats, iters, weights)
+
+
+def trap_window(ys, xs, margin=4.0, oversample=8):
+    """The far-field window that shows every given trap position (any shape:
+    one list, a batch, a whole trajectory): the bounding box of the positions
+    widened by `margin` far-field pixels on every side, sampled at 1/oversample
+    of a pixel, the origin snapped outwards to a multiple of the pitch so that
+    every whole bin inside is a sample point. Returns (origin, pitch, size) as
+    farfield_zoom takes them. Pure host code."""
+    oversample = int(oversample)
+    margin = float(margin)
+    if oversample < 1:
+        raise ValueError(f"oversample must be a positive whole number, got {oversample}")
+    if not (np.isfinite(margin) and margin >= 0):
+        raise ValueError(f"margin must be finite and >= 0, got {margin}")
+    origin, size = [], []
+    for name, v in (("ys", ys), ("xs", xs)):
+        v = np.asarray(v, dtype=np.float64)
+        if v.size == 0 or not np.all(np.isfinite(v)):
+            raise ValueError(f"{name} must hold at least one position, all finite")
+        first = int(np.floor((v.min() - margin) * oversample))  # in samples from bin 0
+        last = int(np.ceil((v.max() + margin) * oversample))
+        n = last - first + 1
+        if n > _lib.ZOOM_MAX_SAMPLES:
+            raise ValueError(f"the window along {name} would have {n} samples, above {_lib.ZOOM_MAX_SAMPLES}: lower "
+                             f"oversample ({oversample}) or margin ({margin}), or preview fewer traps at once")
+        origin.append(first / oversample)
+        size.append(n)
+    return (origin[0], origin[1]), (1.0 / oversample, 1.0 / oversample), (size[0], size[1])
+
+
+def expected_outcome(hologram_or_frame, window, z=0.0, ain=None, ct2pi=None):
+    """The far-field intensity a hologram (floating phase, [H][W] or
+    [B][H][W]) or a uint8 SLM frame (with its ct2pi) produces on `window` =
+    (origin, pitch, size), as trap_window returns it, in the focal plane of the
+    defocus z: _lib.farfield_zoom, float32 [..][ny][nx]. A frame is previewed as
+    it is displayed: no correction mask is taken off."""
+    origin, pitch, size = window
+    return _lib.farfield_zoom(hologram_or_frame, origin, pitch, size, z=z, ain=ain, ct2pi=ct2pi)
 
 
 def trap_frame(shape, coords, which, mask=None, mask_flag: bool = True, ct2pi=256):
