@@ -587,6 +587,75 @@ int slm_farfield_zoom_timed(const void* hologram, int kind, int batch, int heigh
                             double ct2pi, double y0, double x0, double dy, double dx, int ny, int nx, double z,
                             float* intensity, double* field, double* kernel_us);
 
+/* ---- resident zoom: the zoomed far field with stream, buffers and tables kept --
+ * The same far field on a handle that keeps what the one-shot creates and frees
+ * per call, runs all holograms of a call in the same launches (in groups that
+ * bound the work buffers), gives each hologram a window of its own if asked,
+ * takes a correction mask off, and reads the uint8 frames of the last trap or
+ * image sequence where they already are, on the device. Without a mask a
+ * sample is the one-shot's, bit for bit: the kernels, the tables and the
+ * accumulation (chunks of 256 pixels, added in float64 in their order) are the
+ * same, and a sample's value depends on its own position, the pixel indices,
+ * the hologram, a_in, the mask and z; never on the number of holograms in the
+ * run, the group a hologram falls in, the band, whether the first product split
+ * its columns, or whether the windows are shared.
+ * With a mask, per pixel: arg = t - mask[k][l] (one rounded float64
+ * subtraction), t = 2 pi level / ct2pi as the one-shot's level table evaluates
+ * it, or (double)phase for SLM_ZOOM_PHASE_F32; u = the float64 sine and cosine
+ * of arg rounded to complex64, times a_in as before.
+ * slm_zoom_create: `batch` (1 .. 1024) holograms per run at most, sides as the
+ *   one-shot, windows of up to max_ny x max_nx (1 .. 4096) samples. Creates the
+ *   stream; buffers are sized at need, only grow, and go with the handle.
+ *   $SLM_ZOOM_PARTIAL_BYTES (a positive whole number, read here) replaces the two
+ *   caps of the partial buffers (64 MB for the second product, 128 MB for the
+ *   split first product); anything else in it gives SLM_ERR_ARG.
+ * slm_zoom_set_ain: [h][w], NULL = ones; checked as the one-shot's.
+ * slm_zoom_set_mask: [h][w] float64 radians, NULL = none; a non-finite entry
+ *   gives SLM_ERR_ARG.
+ * slm_zoom_set_window: per_hologram == 0: y0, x0, z hold one entry each and the
+ *   tables are shared; otherwise `batch` entries each, and hologram i of a run
+ *   gets origin (y0[i], x0[i]) and defocus z[i]. Pitch and size are shared.
+ *   Builds the tables; no run rebuilds them. Checks and messages are the
+ *   one-shot's; ny > max_ny or nx > max_nx gives SLM_ERR_ARG.
+ * slm_zoom_set_timed: timed != 0: later runs time their kernels with HIP events.
+ * slm_zoom_run: `count` (1 .. batch) holograms [count][h][w] of `kind` from the
+ *   host: one upload, everything enqueued on the handle's stream, no host
+ *   synchronisation. `hologram` must stay valid until slm_zoom_read (or the
+ *   next call on the handle that waits). SLM_ERR_STATE before
+ *   slm_zoom_set_window. (A run with another ct2pi than the last one's uploads
+ *   the 256 level values again.)
+ * slm_zoom_run_spots / slm_zoom_run_plan: the holograms are the uint8 frames
+ *   with flat index f B + b in [first, first + count) of the source's last
+ *   sequence, read from the source's device buffer (kind = levels). The
+ *   handle's stream waits for an event recorded on the source's stream (the
+ *   chain that writes the frames), and the source's stream waits for an event
+ *   recorded after the run (so a later sequence overwrites the frames only
+ *   after they have been read); no host synchronisation. SLM_ERR_STATE: no
+ *   sequence, or one that did not keep its frames; SLM_ERR_ARG: another shape
+ *   than the handle's, a range outside the sequence.
+ * slm_zoom_read: waits for the run; intensity [count][ny][nx] float32, field
+ *   [count][ny][nx][2] float64 (SLM_ERR_STATE if the run had want_field == 0),
+ *   kernel_us[SLM_ZOOM_NUM_KERNEL_CLASSES] (SLM_ERR_STATE unless the run was
+ *   timed; the tables are no part of a run: class 0 is 0). Any pointer may be
+ *   NULL. SLM_ERR_STATE before the first run.
+ * slm_zoom_info: of the last run, info[0] = groups, info[1] = bands per group,
+ *   info[2] = launches of the first product that split their columns (info
+ *   holds 3 ints). SLM_ERR_STATE before the first run.
+ * slm_release_caches does not touch handles: they belong to the caller.       */
+typedef struct slm_zoom slm_zoom;
+int slm_zoom_create(int batch, int height, int width, int max_ny, int max_nx, slm_zoom** out);
+int slm_zoom_destroy(slm_zoom* zm);
+int slm_zoom_set_ain(slm_zoom* zm, const float* ain);
+int slm_zoom_set_mask(slm_zoom* zm, const double* mask);
+int slm_zoom_set_window(slm_zoom* zm, int per_hologram, const double* y0, const double* x0, const double* z,
+                        double dy, double dx, int ny, int nx);
+int slm_zoom_set_timed(slm_zoom* zm, int timed);
+int slm_zoom_run(slm_zoom* zm, const void* hologram, int kind, int count, double ct2pi, int want_field);
+int slm_zoom_run_spots(slm_zoom* zm, slm_spots* sp, int first, int count, double ct2pi, int want_field);
+int slm_zoom_run_plan(slm_zoom* zm, slm_plan* plan, int first, int count, double ct2pi, int want_field);
+int slm_zoom_read(slm_zoom* zm, float* intensity, double* field, double* kernel_us);
+int slm_zoom_info(slm_zoom* zm, int* info);
+
 /* ---- CLI post-processing ------------------------------
  * slm_transform_hologram -> transform_hologram(hologram, args)
  *                           src/generate_hologram.py:82-87: deflect_hologram

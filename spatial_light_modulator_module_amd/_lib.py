@@ -147,6 +147,17 @@ _SIGNATURES = [
                                    _c_double, _c_double, _c_int, _c_int, _c_double, _vp, _vp]),
     ("slm_farfield_zoom_timed", _c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_double, _c_double, _c_double,
                                          _c_double, _c_double, _c_int, _c_int, _c_double, _vp, _vp, _vp]),
+    ("slm_zoom_create", _c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _P(_vp)]),
+    ("slm_zoom_destroy", _c_int, [_vp]),
+    ("slm_zoom_set_ain", _c_int, [_vp, _vp]),
+    ("slm_zoom_set_mask", _c_int, [_vp, _vp]),
+    ("slm_zoom_set_window", _c_int, [_vp, _c_int, _vp, _vp, _vp, _c_double, _c_double, _c_int, _c_int]),
+    ("slm_zoom_set_timed", _c_int, [_vp, _c_int]),
+    ("slm_zoom_run", _c_int, [_vp, _vp, _c_int, _c_int, _c_double, _c_int]),
+    ("slm_zoom_run_spots", _c_int, [_vp, _vp, _c_int, _c_int, _c_double, _c_int]),
+    ("slm_zoom_run_plan", _c_int, [_vp, _vp, _c_int, _c_int, _c_double, _c_int]),
+    ("slm_zoom_read", _c_int, [_vp, _vp, _vp, _vp]),
+    ("slm_zoom_info", _c_int, [_vp, _vp]),
 ]
 
 ZOOM_PHASE_F32 = 0
@@ -159,6 +170,7 @@ ZOOM_NUM_KERNEL_CLASSES = 4
 ZOOM_KERNEL_CLASS_NAMES = ("tables", "field", "rows", "cols")
 ZOOM_MIN_SIDE, ZOOM_MAX_SIDE = 2, 4096  # hologram sides
 ZOOM_MAX_SAMPLES = 4096  # per window side
+ZOOM_MAX_BATCH = 1024  # holograms per run of a Zoom handle
 
 SPOTS_KERNEL_FIELDS = 0
 SPOTS_KERNEL_UPDATE = 1
@@ -762,6 +774,60 @@ def _pair(v, name, kind=float):
     return float(p[0]), float(p[1])
 
 
+def _zoom_holograms(hologram, ct2pi):
+    """(holograms [B][H][W] contiguous, float32 phases or uint8 levels, the kind,
+    whether one [H][W] was given); ValueError on anything else."""
+    holo = np.asarray(hologram)
+    if holo.ndim not in (2, 3):
+        raise ValueError(f"a hologram is [H][W] or [B][H][W], got shape {holo.shape}")
+    if holo.dtype == np.uint8:
+        kind = ZOOM_LEVELS_U8
+        _zoom_check_ct2pi(ct2pi)
+    elif np.issubdtype(holo.dtype, np.floating):
+        kind = ZOOM_PHASE_F32
+        holo = holo.astype(np.float32, copy=False)
+    else:
+        raise ValueError(f"a hologram is a floating phase or a uint8 frame, got dtype {holo.dtype}")
+    single = holo.ndim == 2
+    holo = np.ascontiguousarray(holo[None] if single else holo)
+    if holo.shape[0] < 1:
+        raise ValueError("the batch holds no hologram")
+    return holo, kind, single
+
+
+def _zoom_check_ct2pi(ct2pi):
+    if ct2pi is None or not np.isfinite(ct2pi) or not ct2pi > 0:
+        raise ValueError(f"a uint8 frame needs ct2pi finite and positive, got {ct2pi!r}")
+
+
+def _zoom_check_sides(h, w):
+    if not (ZOOM_MIN_SIDE <= h <= ZOOM_MAX_SIDE and ZOOM_MIN_SIDE <= w <= ZOOM_MAX_SIDE):
+        raise ValueError(f"the zoom runs on sides {ZOOM_MIN_SIDE} .. {ZOOM_MAX_SIDE}, got {h} x {w}")
+
+
+def _zoom_check_window(positions, dy, dx, ny, nx):
+    """positions: every origin coordinate and defocus of the window(s)."""
+    if not (1 <= ny <= ZOOM_MAX_SAMPLES and 1 <= nx <= ZOOM_MAX_SAMPLES):
+        raise ValueError(f"a window has 1 .. {ZOOM_MAX_SAMPLES} samples per side, got {ny} x {nx}")
+    if not (np.all(np.isfinite(positions)) and np.isfinite(dy) and np.isfinite(dx)):
+        raise ValueError("the window's origin, pitch and defocus must be finite")
+    if not (dy > 0 and dx > 0):
+        raise ValueError(f"the pitch must be positive, got {dy} x {dx}")
+
+
+def _zoom_ain(ain, h, w):
+    if ain is None:
+        return None
+    a = np.ascontiguousarray(ain, dtype=np.float32)
+    if a.shape != (h, w):
+        raise ValueError(f"ain has shape {a.shape}, the hologram {(h, w)}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError("ain has a non-finite entry")
+    if not np.any(a):
+        raise ValueError("ain is zero everywhere")
+    return a
+
+
 def farfield_zoom(hologram, origin, pitch, size, z=0.0, ain=None, ct2pi=None, return_field=False, timed=False):
     """slm_farfield_zoom: the far field of a hologram on the ny x nx samples
     y_j = origin[0] + j pitch[0], x_i = origin[1] + i pitch[1] (far-field
@@ -775,41 +841,12 @@ def farfield_zoom(hologram, origin, pitch, size, z=0.0, ain=None, ct2pi=None, re
     with return_field also V complex128; with timed also the microseconds per
     kernel class (ZOOM_KERNEL_*) HIP events measured. Every argument is checked here
     (ValueError) before the device is touched."""
-    holo = np.asarray(hologram)
-    if holo.ndim not in (2, 3):
-        raise ValueError(f"a hologram is [H][W] or [B][H][W], got shape {holo.shape}")
-    if holo.dtype == np.uint8:
-        kind = ZOOM_LEVELS_U8
-        if ct2pi is None or not np.isfinite(ct2pi) or not ct2pi > 0:
-            raise ValueError(f"a uint8 frame needs ct2pi finite and positive, got {ct2pi!r}")
-    elif np.issubdtype(holo.dtype, np.floating):
-        kind = ZOOM_PHASE_F32
-        holo = holo.astype(np.float32, copy=False)
-    else:
-        raise ValueError(f"a hologram is a floating phase or a uint8 frame, got dtype {holo.dtype}")
-    single = holo.ndim == 2
-    holo = np.ascontiguousarray(holo[None] if single else holo)
+    holo, kind, single = _zoom_holograms(hologram, ct2pi)
     b, h, w = holo.shape
-    if b < 1:
-        raise ValueError("the batch holds no hologram")
-    if not (ZOOM_MIN_SIDE <= h <= ZOOM_MAX_SIDE and ZOOM_MIN_SIDE <= w <= ZOOM_MAX_SIDE):
-        raise ValueError(f"the zoom runs on sides {ZOOM_MIN_SIDE} .. {ZOOM_MAX_SIDE}, got {h} x {w}")
+    _zoom_check_sides(h, w)
     (y0, x0), (dy, dx), (ny, nx) = _pair(origin, "origin"), _pair(pitch, "pitch"), _pair(size, "size", int)
-    if not (1 <= ny <= ZOOM_MAX_SAMPLES and 1 <= nx <= ZOOM_MAX_SAMPLES):
-        raise ValueError(f"a window has 1 .. {ZOOM_MAX_SAMPLES} samples per side, got {ny} x {nx}")
-    if not all(np.isfinite(v) for v in (y0, x0, dy, dx, float(z))):
-        raise ValueError("the window's origin, pitch and defocus must be finite")
-    if not (dy > 0 and dx > 0):
-        raise ValueError(f"the pitch must be positive, got {dy} x {dx}")
-    a = None
-    if ain is not None:
-        a = np.ascontiguousarray(ain, dtype=np.float32)
-        if a.shape != (h, w):
-            raise ValueError(f"ain has shape {a.shape}, the hologram {(h, w)}")
-        if not np.all(np.isfinite(a)):
-            raise ValueError("ain has a non-finite entry")
-        if not np.any(a):
-            raise ValueError("ain is zero everywhere")
+    _zoom_check_window((y0, x0, float(z)), dy, dx, ny, nx)
+    a = _zoom_ain(ain, h, w)
     out = np.empty((b, ny, nx), np.float32)
     field = np.empty((b, ny, nx), np.complex128) if return_field else None
     us = np.zeros(ZOOM_NUM_KERNEL_CLASSES, np.float64) if timed else None
@@ -823,6 +860,181 @@ def farfield_zoom(hologram, origin, pitch, size, z=0.0, ain=None, ct2pi=None, re
     if timed:
         res.append(us)
     return res[0] if len(res) == 1 else tuple(res)
+
+
+class Zoom:
+    """The resident zoomed far field (slm_zoom_* in include/slm_hip.h): up to
+    `batch` holograms of height x width per run in the same launches, on windows
+    of up to max_size = (ny, nx) samples (one number for both). Stream, buffers
+    and tables stay with the handle; without a mask a sample is farfield_zoom's,
+    bit for bit. Every argument of every method is checked here (ValueError)
+    before the device is touched; the device handle itself is created by the
+    first call that needs it."""
+
+    def __init__(self, batch: int, height: int, width: int, max_size, timed: bool = False):
+        if int(batch) != batch or not 1 <= batch <= ZOOM_MAX_BATCH:
+            raise ValueError(f"a zoom handle takes 1 .. {ZOOM_MAX_BATCH} holograms per run, got {batch!r}")
+        if int(height) != height or int(width) != width:
+            raise ValueError(f"the sides must be whole numbers, got {height!r} x {width!r}")
+        _zoom_check_sides(height, width)
+        max_ny, max_nx = _pair(max_size, "max_size", int)
+        if not (1 <= max_ny <= ZOOM_MAX_SAMPLES and 1 <= max_nx <= ZOOM_MAX_SAMPLES):
+            raise ValueError(f"a window has 1 .. {ZOOM_MAX_SAMPLES} samples per side, got {max_ny} x {max_nx}")
+        self.batch, self.height, self.width = int(batch), int(height), int(width)
+        self.max_size = (max_ny, max_nx)
+        self.timed = bool(timed)
+        self.size = None  # (ny, nx) of the window in force
+        self.per_hologram = False
+        self.handle = None
+        self._lib = None
+        self._ran = None  # (count, (ny, nx), with the field) of the last run
+        self._held = None  # the host array of the last run: the upload may still read it
+
+    def _h(self):
+        """The device handle, created at the first need."""
+        if self.handle is None:
+            init()
+            self._lib = load()
+            h = ctypes.c_void_p()
+            check(self._lib.slm_zoom_create(self.batch, self.height, self.width, self.max_size[0], self.max_size[1],
+                                            ctypes.byref(h)), "slm_zoom_create")
+            self.handle = h
+            check(self._lib.slm_zoom_set_timed(h, int(self.timed)), "slm_zoom_set_timed")
+        return self.handle
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self._lib.slm_zoom_destroy(self.handle)
+            self.handle = None
+        self._held = None
+
+    def __del__(self):  # pragma: no cover - best effort
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def set_ain(self, ain) -> None:
+        """ain [H][W] shared by every hologram; None = ones."""
+        a = _zoom_ain(ain, self.height, self.width)
+        h = self._h()
+        check(self._lib.slm_zoom_set_ain(h, ptr(a)), "slm_zoom_set_ain")
+
+    def set_mask(self, mask) -> None:
+        """The correction mask [H][W] (float64 radians) the holograms carry: it is
+        taken off, the field is exp(i (phase - mask)). None = no mask."""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, dtype=np.float64)
+            if m.shape != (self.height, self.width):
+                raise ValueError(f"the mask has shape {m.shape}, the holograms {(self.height, self.width)}")
+            if not np.all(np.isfinite(m)):
+                raise ValueError("the mask has a non-finite entry")
+        h = self._h()
+        check(self._lib.slm_zoom_set_mask(h, ptr(m)), "slm_zoom_set_mask")
+
+    def set_window(self, origin, pitch, size, z=0.0) -> None:
+        """One window (origin = (y0, x0), z a number) for every hologram, or one per
+        hologram: origin [batch][2] and / or z [batch]; hologram i of a run then
+        gets origin[i] and z[i]. Pitch and size are shared. Builds the tables."""
+        o = np.asarray(origin, dtype=np.float64)
+        zz = np.asarray(z, dtype=np.float64)
+        if o.shape not in ((2,), (self.batch, 2)):
+            raise ValueError(f"origin is (y0, x0) or an array [batch {self.batch}][2], got shape {o.shape}")
+        if zz.shape not in ((), (self.batch,)):
+            raise ValueError(f"z is one number or an array [batch {self.batch}], got shape {zz.shape}")
+        (dy, dx), (ny, nx) = _pair(pitch, "pitch"), _pair(size, "size", int)
+        _zoom_check_window(np.concatenate([o.ravel(), zz.ravel()]), dy, dx, ny, nx)
+        if ny > self.max_size[0] or nx > self.max_size[1]:
+            raise ValueError(f"a window of {ny} x {nx} samples exceeds the handle's {self.max_size[0]} x "
+                             f"{self.max_size[1]}")
+        per = o.ndim == 2 or zz.ndim == 1
+        n = self.batch if per else 1
+        o2 = np.broadcast_to(o, (n, 2))
+        y0, x0 = np.ascontiguousarray(o2[:, 0]), np.ascontiguousarray(o2[:, 1])
+        z1 = np.ascontiguousarray(np.broadcast_to(zz, (n,)))
+        h = self._h()
+        check(self._lib.slm_zoom_set_window(h, int(per), ptr(y0), ptr(x0), ptr(z1), dy, dx, ny, nx),
+              "slm_zoom_set_window")
+        self.size, self.per_hologram = (ny, nx), per
+
+    def _check_run(self, count, ct2pi, levels):
+        if self.size is None:
+            raise ValueError("run before set_window")
+        if not 1 <= count <= self.batch:
+            raise ValueError(f"a run takes 1 .. {self.batch} holograms (the handle's batch), got {count}")
+        if levels:
+            _zoom_check_ct2pi(ct2pi)
+
+    def run(self, holograms, ct2pi=None, return_field: bool = False) -> None:
+        """`holograms` [count][H][W] (or one [H][W]) as farfield_zoom takes them,
+        count <= batch: one upload, everything enqueued; read() waits."""
+        holo, kind, _ = _zoom_holograms(holograms, ct2pi)
+        if holo.shape[1:] != (self.height, self.width):
+            raise ValueError(f"the holograms are {holo.shape[1:]}, the handle's {(self.height, self.width)}")
+        self._check_run(holo.shape[0], ct2pi, kind == ZOOM_LEVELS_U8)
+        h = self._h()
+        self._held = holo
+        check(self._lib.slm_zoom_run(h, ptr(holo), kind, holo.shape[0], float(ct2pi or 0.0), int(bool(return_field))),
+              "slm_zoom_run")
+        self._ran = (holo.shape[0], self.size, bool(return_field))
+
+    def _run_frames(self, source, fn_name, first, count, ct2pi, return_field):
+        if int(first) != first or int(count) != count:
+            raise ValueError(f"first and count must be whole numbers, got {first!r} and {count!r}")
+        if (source.height, source.width) != (self.height, self.width):
+            raise ValueError(f"the frames are {(source.height, source.width)}, the handle's holograms "
+                             f"{(self.height, self.width)}")
+        seq = getattr(source, "_seq", None)
+        if not seq or not getattr(source, "handle", None):
+            raise ValueError("the source holds no sequence")
+        self._check_run(count, ct2pi, True)
+        total = seq[0] * source.batch
+        if first < 0 or first + count > total:
+            raise ValueError(f"frames {first} .. {first + count - 1} lie outside the sequence's {total}")
+        h = self._h()
+        check(getattr(self._lib, fn_name)(h, source.handle, int(first), int(count), float(ct2pi),
+                                          int(bool(return_field))), fn_name)
+        self._ran = (int(count), self.size, bool(return_field))
+
+    def run_spots(self, spots: "Spots", first: int, count: int, ct2pi, return_field: bool = False) -> None:
+        """The uint8 frames f B + b in [first, first + count) of the last
+        Spots.sequence, read where they are on the device, ordered after the
+        chain that writes them (and a later sequence after this run)."""
+        self._run_frames(spots, "slm_zoom_run_spots", first, count, ct2pi, return_field)
+
+    def run_plan(self, plan: "Plan", first: int, count: int, ct2pi, return_field: bool = False) -> None:
+        """As run_spots, for the frames of the last Plan.sequence."""
+        self._run_frames(plan, "slm_zoom_run_plan", first, count, ct2pi, return_field)
+
+    def read(self):
+        """Waits for the last run: the float32 intensity [count][ny][nx]; after a
+        run with return_field also V complex128; on a timed handle also the
+        microseconds per kernel class (ZOOM_KERNEL_*; the tables are no part of
+        a run)."""
+        if self._ran is None:
+            raise ValueError("read before a run")
+        count, (ny, nx), with_field = self._ran
+        out = np.empty((count, ny, nx), np.float32)
+        field = np.empty((count, ny, nx), np.complex128) if with_field else None
+        us = np.zeros(ZOOM_NUM_KERNEL_CLASSES, np.float64) if self.timed else None
+        check(self._lib.slm_zoom_read(self.handle, ptr(out), None if field is None else field.ctypes.data, ptr(us)),
+              "slm_zoom_read")
+        self._held = None
+        res = [out] + ([field] if with_field else []) + ([us] if self.timed else [])
+        return res[0] if len(res) == 1 else tuple(res)
+
+    def info(self) -> dict:
+        """How the last run was cut (slm_zoom_info)."""
+        a = np.zeros(3, np.int32)
+        check(self._lib.slm_zoom_info(self._h(), ptr(a)), "slm_zoom_info")
+        return {"groups": int(a[0]), "bands": int(a[1]), "split_launches": int(a[2])}
 
 
 def fft2(x: np.ndarray, inverse: bool = False) -> np.ndarray:

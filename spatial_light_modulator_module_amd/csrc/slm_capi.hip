@@ -22,6 +22,7 @@
 #include "generic.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
+#include "seq_frames.hpp"
 
 using namespace slm;
 
@@ -91,6 +92,17 @@ int Engine::mraf_refresh(PlanState&, bool, int*) {
 }
 int Engine::read_trace(PlanState&, int, unsigned long long*) {
     return fail(SLM_ERR_STATE, "no trace buffer (set SLM_TRACE_BUF=1 before creating the plan)");
+}
+
+// the resident zoom's door to the frames of the last sequence (seq_frames.hpp)
+SeqFrames plan_seq_frames(const slm_plan* p) {
+    SeqFrames q;
+    q.stream = p->s.stream;
+    q.n = p->seq.n_frames * p->s.B;
+    q.H = p->s.H;
+    q.W = p->s.W;
+    if (p->seq.n_frames && p->seq.has_frames) q.frames = p->seq.frames.p;
+    return q;
 }
 
 }  // namespace slm

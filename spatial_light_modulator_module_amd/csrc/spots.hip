@@ -56,6 +56,7 @@
 
 #include "quantize.hpp"
 #include "runtime.hpp"
+#include "seq_frames.hpp"
 #include "spot_tiles.hpp"  // the tile constants, acc_row, mfma and table_entry (shared with zoom.hip)
 
 namespace {
@@ -499,6 +500,17 @@ struct slm_spots {
     DevBuf<double> seq_mask;    // [H][W]
     DevBuf<double> seq_w_last;  // [B][Mp]: the weights the last sequence ended with (resume)
 };
+
+// the resident zoom's door to the frames of the last sequence (seq_frames.hpp)
+slm::SeqFrames slm::spots_seq_frames(const slm_spots* s) {
+    SeqFrames q;
+    q.stream = s->stream;
+    q.n = s->seq_frames * s->B;
+    q.H = s->H;
+    q.W = s->W;
+    if (s->seq_frames && s->seq_has_frames) q.frames = s->seq_out.p;
+    return q;
+}
 
 namespace {
 

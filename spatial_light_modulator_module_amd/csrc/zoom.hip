@@ -34,14 +34,25 @@
 // indices alone: never on the window around it, the tile it sits in, whether
 // the columns were split, or the batch. The window is worked off in bands of
 // whole tile rows that bound the partial buffer.
+//
+// Two hosts drive the kernels. The one-shot (slm_farfield_zoom) creates and
+// frees everything per call and runs hologram by hologram. The resident zoom
+// (slm_zoom_*; DESIGN.md section 3, "Resident zoom") keeps stream, buffers and
+// tables, takes a group of holograms through each launch (a window per
+// hologram if asked), takes a correction mask off in the field pass, and reads
+// the frames of a sequence in place (seq_frames.hpp), ordered with the
+// sequence's stream by events in both directions. By the accumulation rule
+// above neither the group, the band nor the split moves a bit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <vector>
 
 #include "runtime.hpp"
+#include "seq_frames.hpp"
 #include "spot_tiles.hpp"
 
 namespace {
@@ -58,45 +69,83 @@ constexpr int kSplitBelowWaves = 4096;
 constexpr size_t kRowsPartialBytes = 128u << 20;
 
 // ---- tables ---------------------------------------------------------------
-// P[n][s] = exp(i f_s(n)) for sample s < count at pos0 + s pitch, 0 for the padding; [N][padded]
-__global__ void __launch_bounds__(256) zoom_table_kernel(float2* out, int N, int count, int padded, double pos0,
-                                                         double pitch, double z) {
-    const long long n_el = (long long)N * padded;
+// Every kernel below serves a group of holograms in one launch: the hologram's
+// index within the group rides in the grid (blockIdx.y of the element-wise
+// kernels, blockIdx.z / units of the products), and a table is reached at
+// base + hologram * stride, the stride 0 where the holograms share a window.
+// The one-shot launches them with groups of one hologram.
+
+// P[n][s] = exp(i f_s(n)) for sample s < count at pos0 + s pitch, 0 for the padding; [windows][N][padded],
+// window blockIdx.y at pos0s[window] with zs[window], or at (pos0, z) where pos0s is null
+struct TableParams {
+    float2* out;
+    const double *pos0s, *zs;  // [windows] on the device, or nullptr
+    double pos0, pitch, z;
+    int N, count, padded;
+};
+
+__global__ void __launch_bounds__(256) zoom_table_kernel(TableParams p) {
+    const long long n_el = (long long)p.N * p.padded;
+    const double pos0 = p.pos0s ? p.pos0s[blockIdx.y] : p.pos0, z = p.pos0s ? p.zs[blockIdx.y] : p.z;
+    float2* out = p.out + (size_t)blockIdx.y * n_el;
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n_el; i += (long long)gridDim.x * 256) {
-        const int n = (int)(i / padded), s = (int)(i - (long long)n * padded);
+        const int n = (int)(i / p.padded), s = (int)(i - (long long)n * p.padded);
         float2 v = make_float2(0.0f, 0.0f);
         // pos0 + s pitch with the product rounded before the sum (no contraction into an fma)
-        if (s < count) v = table_entry(n, N, __dadd_rn(pos0, __dmul_rn((double)s, pitch)), z);
+        if (s < p.count) v = table_entry(n, p.N, __dadd_rn(pos0, __dmul_rn((double)s, p.pitch)), z);
         out[i] = v;
     }
 }
 
 // ---- the field a u --------------------------------------------------------
 // kind SLM_ZOOM_PHASE_F32: u = float64 sincos of the float32 phase, as spot_phase_kernel forms it;
-// SLM_ZOOM_LEVELS_U8: u = levels[level], the 256 entries evaluated in float64 on the host
-__global__ void __launch_bounds__(256) zoom_field_kernel(const void* holo, int kind, const float* ain,
-                                                         const float2* levels, float2* field, long long n) {
-    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+// SLM_ZOOM_LEVELS_U8: u = levels[level], the 256 entries evaluated in float64 on the host.
+// With a correction mask (the resident zoom): u = float64 sincos of t - mask, one rounded float64
+// subtraction, t = (double)phase or level_t[level] = 2 pi level / ct2pi as the level table forms it.
+struct FieldParams {
+    const void* holo;       // [holograms][H][W] float32 or uint8
+    const float* ain;       // [H][W] or nullptr
+    const double* mask;     // [H][W] or nullptr
+    const float2* levels;   // [256], levels without a mask
+    const double* level_t;  // [256], levels with a mask
+    float2* field;          // [holograms][H][W]
+    long long n;            // H W
+    int kind;
+};
+
+__global__ void __launch_bounds__(256) zoom_field_kernel(FieldParams p) {
+    const size_t base = (size_t)blockIdx.y * p.n;
+    const uint8_t* lv = static_cast<const uint8_t*>(p.holo) + base;
+    const float* ph = static_cast<const float*>(p.holo) + base;
+    float2* field = p.field + base;
+    for (long long i = blockIdx.x * 256LL + threadIdx.x; i < p.n; i += (long long)gridDim.x * 256) {
         float2 u;
-        if (kind == SLM_ZOOM_LEVELS_U8) {
-            u = levels[static_cast<const uint8_t*>(holo)[i]];
+        if (p.mask) {
+            const double t = p.kind == SLM_ZOOM_LEVELS_U8 ? p.level_t[lv[i]] : (double)ph[i];
+            double s, c;
+            sincos(__dsub_rn(t, p.mask[i]), &s, &c);
+            u = make_float2((float)c, (float)s);
+        } else if (p.kind == SLM_ZOOM_LEVELS_U8) {
+            u = p.levels[lv[i]];
         } else {
             double s, c;
-            sincos((double)static_cast<const float*>(holo)[i], &s, &c);
+            sincos((double)ph[i], &s, &c);
             u = make_float2((float)c, (float)s);
         }
-        const float a = ain ? ain[i] : 1.0f;
+        const float a = p.ain ? p.ain[i] : 1.0f;
         field[i] = make_float2(u.x * a, u.y * a);
     }
 }
 
 // ---- product 1: R = (a u) conj(Px) ----------------------------------------
 struct RowsParams {
-    const float2* field;  // [H][W]
-    const float2* px;     // [W][nxp]
-    float2* out;          // R [H][nxp], or with a split the chunk results [chunks][H][nxp]
+    const float2* field;  // [holograms][H][W]
+    const float2* px;     // [W][nxp] of the group's first hologram
+    float2* out;          // R [holograms][H][nxp], or with a split the chunk results [holograms][chunks][H][nxp]
+    size_t px_stride;     // elements between the tables of two holograms (0: shared)
     int H, W, nxp;
-    int cols_per_unit;    // columns per blockIdx.z: all of them, or with a split one chunk
+    int cols_per_unit;    // columns per unit: all of them, or with a split one chunk
+    int units;            // units per hologram: blockIdx.z = hologram * units + unit
 };
 
 // One workgroup per 32 rows x 128 samples: its four waves share the staged
@@ -105,14 +154,16 @@ struct RowsParams {
 // stage. A window of few sample tiles splits the columns over workgroups, one
 // chunk each, and zoom_rows_fold_kernel adds the chunk results as this kernel
 // adds them in its registers otherwise: R is the same bit for bit either way.
-// grid = (groups of 4 sample tiles, row tiles, 1 or chunks).
+// grid = (groups of 4 sample tiles, row tiles, holograms x (1 or chunks)).
 __global__ void __launch_bounds__(kThreads) zoom_rows_kernel(RowsParams p) {
     __shared__ float tiles[2][kTile * kLdsStride];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
     const int row0 = blockIdx.y * kTile, s0 = (blockIdx.x * kWaves + wave) * kTile;
     const bool active = s0 < p.nxp;
-    const int c_begin = blockIdx.z * p.cols_per_unit, c_end = min(p.W, c_begin + p.cols_per_unit);
-    const float2* px = p.px + (active ? s0 : 0) + li;
+    const int holo = blockIdx.z / p.units, unit = blockIdx.z - holo * p.units;
+    const int c_begin = unit * p.cols_per_unit, c_end = min(p.W, c_begin + p.cols_per_unit);
+    const float2* field = p.field + (size_t)holo * p.H * p.W;
+    const float2* px = p.px + (size_t)holo * p.px_stride + (active ? s0 : 0) + li;
 
     f32x16 are, aim;
     double dre[16], dim[16];
@@ -130,7 +181,7 @@ __global__ void __launch_bounds__(kThreads) zoom_rows_kernel(RowsParams p) {
         for (int e = 0; e < 4; ++e) {
             const int gr = row0 + tr + 8 * e, gc = c0 + tc;
             ft[e] = make_float2(0.0f, 0.0f);
-            if (gr < p.H && gc < p.W) ft[e] = p.field[(size_t)gr * p.W + gc];
+            if (gr < p.H && gc < p.W) ft[e] = field[(size_t)gr * p.W + gc];
         }
     };
     constexpr int kSteps = kTile / 2;  // a step = 2 columns
@@ -185,9 +236,12 @@ __global__ void __launch_bounds__(kThreads) zoom_rows_kernel(RowsParams p) {
     }
 }
 
-// R = the chunk results of a split first product, added in float64 in their order and rounded once
+// R = the chunk results of a split first product, added in float64 in their order and rounded once;
+// partial [holograms][chunks][n], r [holograms][n], hologram blockIdx.y
 __global__ void __launch_bounds__(256) zoom_rows_fold_kernel(const float2* partial, float2* r, int chunks,
                                                              long long n) {
+    partial += (size_t)blockIdx.y * chunks * n;
+    r += (size_t)blockIdx.y * n;
     for (long long e = blockIdx.x * 256LL + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
         double re = 0.0, im = 0.0;
         for (int c = 0; c < chunks; ++c) {
@@ -201,22 +255,25 @@ __global__ void __launch_bounds__(256) zoom_rows_fold_kernel(const float2* parti
 
 // ---- product 2: V chunks = conj(Py) R -------------------------------------
 struct ColsParams {
-    const float2* py;  // [H][nyp]
-    const float2* r;   // [H][nxp]
-    float2* partial;   // [chunks][band rows][nxp]
+    const float2* py;  // [H][nyp] of the group's first hologram
+    const float2* r;   // [holograms][H][nxp]
+    float2* partial;   // [holograms][chunks][band rows][nxp]
+    size_t py_stride;  // elements between the tables of two holograms (0: shared)
     int H, nyp, nxp;
     int j0, band_rows;  // this band: sample rows j0 .. j0 + band_rows (a multiple of 32)
+    int chunks;         // per hologram: blockIdx.z = hologram * chunks + chunk
 };
 
 // One wave per 32 x 32 output tile and chunk of 256 pixel rows, four adjacent
-// column tiles per workgroup; no barriers. grid = (column tiles / 4, the band's row tiles, chunks).
+// column tiles per workgroup; no barriers. grid = (column tiles / 4, the band's row tiles, holograms x chunks).
 __global__ void __launch_bounds__(kThreads) zoom_cols_kernel(ColsParams p) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, li = lane & 31, lh = lane >> 5;
-    const int i0 = (blockIdx.x * kWaves + wave) * kTile, jb = blockIdx.y * kTile, chunk = blockIdx.z;
+    const int i0 = (blockIdx.x * kWaves + wave) * kTile, jb = blockIdx.y * kTile;
+    const int holo = blockIdx.z / p.chunks, chunk = blockIdx.z - holo * p.chunks;
     if (i0 >= p.nxp) return;
     const int k0 = chunk * kChunk;
-    const float2* py = p.py + p.j0 + jb + li;
-    const float2* rr = p.r + i0 + li;
+    const float2* py = p.py + (size_t)holo * p.py_stride + p.j0 + jb + li;
+    const float2* rr = p.r + (size_t)holo * p.H * p.nxp + i0 + li;
     f32x16 vre, vim;
 #pragma unroll
     for (int r = 0; r < 16; ++r) vre[r] = vim[r] = 0.0f;
@@ -251,31 +308,36 @@ __global__ void __launch_bounds__(kThreads) zoom_cols_kernel(ColsParams p) {
             b[s] = bn[s];
         }
     }
-    float2* out = p.partial + ((size_t)chunk * p.band_rows + jb) * p.nxp + i0 + li;
+    float2* out = p.partial + ((size_t)blockIdx.z * p.band_rows + jb) * p.nxp + i0 + li;
 #pragma unroll
     for (int r = 0; r < 16; ++r) out[(size_t)acc_row(r, lh) * p.nxp] = make_float2(vre[r], vim[r]);
 }
 
 // ---- fold: V = the chunks added in float64 in their order, I = |V|^2 ------
 struct FoldParams {
-    const float2* partial;  // [chunks][band rows][nxp]
-    float* intensity;       // [rows][nx]
-    double2* v;             // [rows][nx] or nullptr
+    const float2* partial;  // [holograms][chunks][band rows][nxp]
+    float* intensity;       // the band's [rows][nx] of the group's first hologram
+    double2* v;             // likewise, or nullptr
+    size_t out_stride;      // elements between the outputs of two holograms
     int chunks, band_rows, rows, nx, nxp;  // rows = the band's samples that exist (<= band_rows)
 };
 
+// hologram blockIdx.y
 __global__ void __launch_bounds__(256) zoom_fold_kernel(FoldParams p) {
     const long long n = (long long)p.rows * p.nx;
+    const float2* partial = p.partial + (size_t)blockIdx.y * p.chunks * p.band_rows * p.nxp;
+    float* intensity = p.intensity + blockIdx.y * p.out_stride;
+    double2* v = p.v ? p.v + blockIdx.y * p.out_stride : nullptr;
     for (long long e = blockIdx.x * 256LL + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
         const int j = (int)(e / p.nx), i = (int)(e - (long long)j * p.nx);
         double vr = 0.0, vi = 0.0;
         for (int c = 0; c < p.chunks; ++c) {
-            const float2 t = p.partial[((size_t)c * p.band_rows + j) * p.nxp + i];
+            const float2 t = partial[((size_t)c * p.band_rows + j) * p.nxp + i];
             vr += (double)t.x;
             vi += (double)t.y;
         }
-        p.intensity[e] = (float)(vr * vr + vi * vi);
-        if (p.v) p.v[e] = make_double2(vr, vi);
+        intensity[e] = (float)(vr * vr + vi * vi);
+        if (v) v[e] = make_double2(vr, vi);
     }
 }
 
@@ -285,74 +347,234 @@ int padded(int n) { return (n + kTile - 1) / kTile * kTile; }
 using slm::DevBuf;
 using slm::fail;
 
-// the call's stream, buffers and (when timed) events, all released when it returns
-struct Zoom {
+// begin / end event pairs around the kernels of each class (events are kept and used again)
+struct Stopwatch {
+    std::vector<hipEvent_t> ev;
+    std::vector<int> cls;  // pair k is ev[2 k], ev[2 k + 1], of class cls[k]
+    size_t used = 0;
+    bool timed = false;
+    ~Stopwatch() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+    void reset(bool on) {
+        timed = on;
+        used = 0;
+        cls.clear();
+    }
+    int mark(hipStream_t st) {
+        if (used == ev.size()) {
+            hipEvent_t e = nullptr;
+            HIP_TRY(hipEventCreate(&e));
+            ev.push_back(e);
+        }
+        HIP_TRY(hipEventRecord(ev[used++], st));
+        return 0;
+    }
+    int begin(int c, hipStream_t st) {
+        if (!timed) return 0;
+        cls.push_back(c);
+        return mark(st);
+    }
+    int end(hipStream_t st) { return timed ? mark(st) : 0; }
+    // after the stream has been waited for
+    int read(double* kernel_us) const {
+        for (int c = 0; c < SLM_ZOOM_NUM_KERNEL_CLASSES; ++c) kernel_us[c] = 0.0;
+        for (size_t k = 0; k < cls.size(); ++k) {
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]));
+            kernel_us[cls[k]] += 1e3 * ms;
+        }
+        return 0;
+    }
+};
+
+// ---- argument checks, shared by the one-shot and the handle ---------------
+int check_kind(int kind) {
+    if (kind != SLM_ZOOM_PHASE_F32 && kind != SLM_ZOOM_LEVELS_U8) return fail(SLM_ERR_ARG, "unknown kind %d", kind);
+    return 0;
+}
+int check_sides(int height, int width) {
+    if (height < kMinSide || width < kMinSide || height > kMaxSide || width > kMaxSide)
+        return fail(SLM_ERR_ARG, "the zoom runs on sides %d .. %d, got %d x %d", kMinSide, kMaxSide, height, width);
+    return 0;
+}
+int check_samples(int ny, int nx) {
+    if (ny < 1 || nx < 1 || ny > kMaxSamples || nx > kMaxSamples)
+        return fail(SLM_ERR_ARG, "a window has 1 .. %d samples per side, got %d x %d", kMaxSamples, ny, nx);
+    return 0;
+}
+int check_pitch(double dy, double dx) {
+    if (!(dy > 0.0) || !(dx > 0.0)) return fail(SLM_ERR_ARG, "the pitch must be positive, got %g x %g", dy, dx);
+    return 0;
+}
+int check_ct2pi(int kind, double ct2pi) {
+    if (kind == SLM_ZOOM_LEVELS_U8 && (!(ct2pi > 0.0) || !std::isfinite(ct2pi)))
+        return fail(SLM_ERR_ARG, "ct2pi must be finite and positive, got %g", ct2pi);
+    return 0;
+}
+int check_ain(const float* ain, size_t holo) {
+    if (!ain) return 0;
+    double sum = 0.0;
+    for (size_t i = 0; i < holo; ++i) {
+        if (!std::isfinite(ain[i])) return fail(SLM_ERR_ARG, "a_in has a non-finite entry");
+        sum += (double)ain[i] * (double)ain[i];
+    }
+    if (!(sum > 0.0)) return fail(SLM_ERR_ARG, "a_in is zero everywhere");
+    return 0;
+}
+const char kNotFinite[] = "the window's origin, pitch and defocus must be finite";
+
+int check_args(const void* hologram, int kind, int batch, int height, int width, const float* ain, double ct2pi,
+               double y0, double x0, double dy, double dx, int ny, int nx, double z, const float* intensity) {
+    if (!hologram || !intensity) return fail(SLM_ERR_ARG, "null argument");
+    RC(check_kind(kind));
+    if (batch < 1) return fail(SLM_ERR_ARG, "batch must be positive, got %d", batch);
+    RC(check_sides(height, width));
+    RC(check_samples(ny, nx));
+    if (!std::isfinite(y0) || !std::isfinite(x0) || !std::isfinite(dy) || !std::isfinite(dx) || !std::isfinite(z))
+        return fail(SLM_ERR_ARG, "%s", kNotFinite);
+    RC(check_pitch(dy, dx));
+    RC(check_ct2pi(kind, ct2pi));
+    return check_ain(ain, (size_t)height * width);
+}
+
+// the 256 level phases t = 2 pi level / ct2pi and their u, evaluated in float64 on the host
+void level_tables(double ct2pi, float2* levels, double* level_t) {
+    for (int v = 0; v < 256; ++v) {
+        const double t = kTwoPi * (double)v / ct2pi;
+        levels[v] = make_float2((float)std::cos(t), (float)std::sin(t));
+        if (level_t) level_t[v] = t;
+    }
+}
+
+int launch_table(hipStream_t st, float2* out, int windows, int N, int count, int padded_count, const double* pos0s,
+                 const double* zs, double pos0, double pitch, double z) {
+    const TableParams tp{out, pos0s, zs, pos0, pitch, z, N, count, padded_count};
+    hipLaunchKernelGGL(zoom_table_kernel, dim3(grid_for((long long)N * padded_count), windows), dim3(256), 0, st, tp);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- one group of holograms through the five kernels ----------------------
+// What a run works on: the device buffers, the window and how the work is cut.
+struct Pass {
+    hipStream_t st;
+    Stopwatch* watch;
+    int H, W, ny, nx, nyp, nxp, kind;
+    const float* ain;
+    const double* mask;
+    const float2* levels;
+    const double* level_t;
+    const float2 *px, *py;         // the tables of hologram 0 of the run
+    size_t px_stride, py_stride;   // 0: one window for all
+    float2 *field, *r, *partial;   // sized for one group
+    int band_rows;
+    size_t rows_partial_bytes;     // the split of product 1 fits these
+};
+
+// product 1 of `n` holograms in one launch splits its columns if the launch's output tiles are few
+bool splits_rows(const Pass& q, int n) {
+    const int row_tiles = (q.H + kTile - 1) / kTile, wchunks = (q.W + kChunk - 1) / kChunk;
+    const size_t r_bytes = (size_t)q.H * q.nxp * sizeof(float2);
+    return wchunks > 1 && (long long)n * row_tiles * (q.nxp / kTile) < kSplitBelowWaves &&
+           (size_t)n * wchunks * r_bytes <= q.rows_partial_bytes;
+}
+
+// `n` holograms at `holo` (device, [n][H][W]), the first of them hologram `first` of the run: the field, R,
+// and band by band V and I into intensity / v, which hold [ny][nx] per hologram `out_stride` elements
+// apart and begin at the group's first hologram. `after_band`, if given, runs after each band's fold
+// (the one-shot copies the band out there). Everything is enqueued; nothing waits.
+template <typename AfterBand>
+int enqueue_group(const Pass& q, const void* holo, int first, int n, float* intensity, double2* v, size_t out_stride,
+                  bool band_outputs, int* split_launches, AfterBand after_band) {
+    const hipStream_t st = q.st;
+    const long long holo_n = (long long)q.H * q.W;
+    const int chunks = (q.H + kChunk - 1) / kChunk, wchunks = (q.W + kChunk - 1) / kChunk;
+    const int row_tiles = (q.H + kTile - 1) / kTile, sample_groups = (q.nxp / kTile + kWaves - 1) / kWaves;
+
+    RC(q.watch->begin(SLM_ZOOM_KERNEL_FIELD, st));
+    const FieldParams fp{holo, q.ain, q.mask, q.levels, q.level_t, q.field, holo_n, q.kind};
+    hipLaunchKernelGGL(zoom_field_kernel, dim3(grid_for(holo_n), n), dim3(256), 0, st, fp);
+    HIP_TRY(hipGetLastError());
+    RC(q.watch->end(st));
+
+    RC(q.watch->begin(SLM_ZOOM_KERNEL_ROWS, st));
+    const bool split = splits_rows(q, n);
+    const int units = split ? wchunks : 1;
+    const RowsParams rp{q.field, q.px + (size_t)first * q.px_stride, split ? q.partial : q.r, q.px_stride, q.H, q.W,
+                        q.nxp, split ? kChunk : wchunks * kChunk, units};
+    hipLaunchKernelGGL(zoom_rows_kernel, dim3(sample_groups, row_tiles, n * units), dim3(kThreads), 0, st, rp);
+    HIP_TRY(hipGetLastError());
+    if (split) {
+        const long long r_el = (long long)q.H * q.nxp;
+        hipLaunchKernelGGL(zoom_rows_fold_kernel, dim3(grid_for(r_el), n), dim3(256), 0, st, q.partial, q.r, wchunks,
+                           r_el);
+        HIP_TRY(hipGetLastError());
+        if (split_launches) ++*split_launches;
+    }
+    RC(q.watch->end(st));
+
+    for (int j0 = 0; j0 < q.ny; j0 += q.band_rows) {
+        const int tile_rows = std::min(q.band_rows, q.nyp - j0), rows = std::min(q.band_rows, q.ny - j0);
+        RC(q.watch->begin(SLM_ZOOM_KERNEL_COLS, st));
+        const ColsParams cp{q.py + (size_t)first * q.py_stride, q.r, q.partial, q.py_stride, q.H, q.nyp, q.nxp, j0,
+                            q.band_rows, chunks};
+        hipLaunchKernelGGL(zoom_cols_kernel, dim3(sample_groups, tile_rows / kTile, n * chunks), dim3(kThreads), 0, st,
+                           cp);
+        HIP_TRY(hipGetLastError());
+        // outputs that hold one band start at the band; outputs that hold the window are entered at row j0
+        const size_t at = band_outputs ? 0 : (size_t)j0 * q.nx;
+        const FoldParams fo{q.partial, intensity + at, v ? v + at : nullptr, out_stride, chunks, q.band_rows, rows,
+                            q.nx, q.nxp};
+        hipLaunchKernelGGL(zoom_fold_kernel, dim3(grid_for((long long)rows * q.nx), n), dim3(256), 0, st, fo);
+        HIP_TRY(hipGetLastError());
+        RC(q.watch->end(st));
+        RC(after_band(j0, rows));
+    }
+    return 0;
+}
+
+// bytes of the partial buffer a group of n holograms needs
+size_t partial_bytes(const Pass& q, int n) {
+    const int chunks = (q.H + kChunk - 1) / kChunk, wchunks = (q.W + kChunk - 1) / kChunk;
+    const size_t cols = (size_t)n * chunks * q.band_rows * q.nxp * sizeof(float2);
+    const size_t rows = splits_rows(q, n) ? (size_t)n * wchunks * q.H * q.nxp * sizeof(float2) : 0;
+    return std::max(cols, rows);
+}
+
+// the band of one hologram: whole tile rows whose chunk results fit `cap` (one tile row always fits)
+int band_rows_for(int H, int nyp, int nxp, size_t cap, int n) {
+    const size_t row_bytes = (size_t)n * ((H + kChunk - 1) / kChunk) * nxp * sizeof(float2);
+    return (int)std::min<size_t>(nyp, std::max<size_t>(kTile, cap / row_bytes / kTile * kTile));
+}
+
+// ---- the one-shot ---------------------------------------------------------
+// the call's stream and buffers, all released when it returns
+struct OneShot {
     hipStream_t stream = nullptr;
     DevBuf<float> ain;
     DevBuf<float2> levels, px, py, field, r, partial;
     DevBuf<uint8_t> holo;
     DevBuf<float> intensity;
     DevBuf<double2> v;
-    std::vector<hipEvent_t> ev;  // begin / end pairs, pair k of class cls[k]
-    std::vector<int> cls;
-    bool timed = false;
-    ~Zoom() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    Stopwatch watch;
+    ~OneShot() {
         if (stream) {
             (void)hipStreamSynchronize(stream);
             (void)hipStreamDestroy(stream);
         }
     }
-    int mark() {
-        hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreate(&e));
-        ev.push_back(e);
-        HIP_TRY(hipEventRecord(e, stream));
-        return 0;
-    }
-    int begin(int c) {
-        if (!timed) return 0;
-        cls.push_back(c);
-        return mark();
-    }
-    int end() { return timed ? mark() : 0; }
 };
 
-int check_args(const void* hologram, int kind, int batch, int height, int width, const float* ain, double ct2pi,
-               double y0, double x0, double dy, double dx, int ny, int nx, double z, const float* intensity) {
-    if (!hologram || !intensity) return fail(SLM_ERR_ARG, "null argument");
-    if (kind != SLM_ZOOM_PHASE_F32 && kind != SLM_ZOOM_LEVELS_U8) return fail(SLM_ERR_ARG, "unknown kind %d", kind);
-    if (batch < 1) return fail(SLM_ERR_ARG, "batch must be positive, got %d", batch);
-    if (height < kMinSide || width < kMinSide || height > kMaxSide || width > kMaxSide)
-        return fail(SLM_ERR_ARG, "the zoom runs on sides %d .. %d, got %d x %d", kMinSide, kMaxSide, height, width);
-    if (ny < 1 || nx < 1 || ny > kMaxSamples || nx > kMaxSamples)
-        return fail(SLM_ERR_ARG, "a window has 1 .. %d samples per side, got %d x %d", kMaxSamples, ny, nx);
-    if (!std::isfinite(y0) || !std::isfinite(x0) || !std::isfinite(dy) || !std::isfinite(dx) || !std::isfinite(z))
-        return fail(SLM_ERR_ARG, "the window's origin, pitch and defocus must be finite");
-    if (!(dy > 0.0) || !(dx > 0.0)) return fail(SLM_ERR_ARG, "the pitch must be positive, got %g x %g", dy, dx);
-    if (kind == SLM_ZOOM_LEVELS_U8 && (!(ct2pi > 0.0) || !std::isfinite(ct2pi)))
-        return fail(SLM_ERR_ARG, "ct2pi must be finite and positive, got %g", ct2pi);
-    if (ain) {
-        const size_t holo = (size_t)height * width;
-        double sum = 0.0;
-        for (size_t i = 0; i < holo; ++i) {
-            if (!std::isfinite(ain[i])) return fail(SLM_ERR_ARG, "a_in has a non-finite entry");
-            sum += (double)ain[i] * (double)ain[i];
-        }
-        if (!(sum > 0.0)) return fail(SLM_ERR_ARG, "a_in is zero everywhere");
-    }
-    return 0;
-}
-
-int zoom_run(Zoom& zm, const void* hologram, int kind, int batch, int H, int W, const float* ain, double ct2pi,
+int zoom_run(OneShot& zm, const void* hologram, int kind, int batch, int H, int W, const float* ain, double ct2pi,
              double y0, double x0, double dy, double dx, int ny, int nx, double z, float* intensity, double* field) {
     HIP_TRY(hipStreamCreateWithFlags(&zm.stream, hipStreamNonBlocking));
     const hipStream_t st = zm.stream;
-    const int nxp = padded(nx), nyp = padded(ny), chunks = (H + kChunk - 1) / kChunk;
+    const int nxp = padded(nx), nyp = padded(ny);
     const size_t holo = (size_t)H * W, el = kind == SLM_ZOOM_LEVELS_U8 ? 1 : sizeof(float);
-    // the band: whole tile rows whose chunk results fit the partial buffer
-    const size_t row_bytes = (size_t)chunks * nxp * sizeof(float2);
-    const int band_rows = std::min<size_t>(nyp, std::max<size_t>(kTile, kPartialBytes / row_bytes / kTile * kTile));
+    Pass q{st, &zm.watch, H, W, ny, nx, nyp, nxp, kind};
+    q.band_rows = band_rows_for(H, nyp, nxp, kPartialBytes, 1);
+    q.rows_partial_bytes = kRowsPartialBytes;
 
     if (ain) RC(zm.ain.need(holo * sizeof(float), st));
     if (kind == SLM_ZOOM_LEVELS_U8) RC(zm.levels.need(256 * sizeof(float2), st));
@@ -361,73 +583,200 @@ int zoom_run(Zoom& zm, const void* hologram, int kind, int batch, int H, int W, 
     RC(zm.holo.need(holo * el, st));
     RC(zm.field.need(holo * sizeof(float2), st));
     RC(zm.r.need((size_t)H * nxp * sizeof(float2), st));
-    // the first product splits its columns over workgroups while its tiles are few (the same R either way)
-    const int row_tiles = (H + kTile - 1) / kTile, wchunks = (W + kChunk - 1) / kChunk;
-    const size_t r_bytes = (size_t)H * nxp * sizeof(float2);
-    const bool split_rows =
-        wchunks > 1 && row_tiles * (nxp / kTile) < kSplitBelowWaves && wchunks * r_bytes <= kRowsPartialBytes;
-    RC(zm.partial.need(std::max(row_bytes * band_rows, split_rows ? wchunks * r_bytes : 0), st));
-    RC(zm.intensity.need((size_t)band_rows * nx * sizeof(float), st));
-    if (field) RC(zm.v.need((size_t)band_rows * nx * sizeof(double2), st));
+    RC(zm.partial.need(partial_bytes(q, 1), st));
+    RC(zm.intensity.need((size_t)q.band_rows * nx * sizeof(float), st));
+    if (field) RC(zm.v.need((size_t)q.band_rows * nx * sizeof(double2), st));
 
     if (ain) RC(slm::copy_sync(zm.ain.p, ain, holo * sizeof(float), hipMemcpyHostToDevice, st));
     if (kind == SLM_ZOOM_LEVELS_U8) {
         float2 levels[256];
-        for (int v = 0; v < 256; ++v) {
-            const double t = kTwoPi * (double)v / ct2pi;
-            levels[v] = make_float2((float)std::cos(t), (float)std::sin(t));
-        }
+        level_tables(ct2pi, levels, nullptr);
         RC(slm::copy_sync(zm.levels.p, levels, sizeof(levels), hipMemcpyHostToDevice, st));
     }
-    RC(zm.begin(SLM_ZOOM_KERNEL_TABLES));
-    hipLaunchKernelGGL(zoom_table_kernel, dim3(grid_for((long long)W * nxp)), dim3(256), 0, st, zm.px.p, W, nx, nxp,
-                       x0, dx, z);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(zoom_table_kernel, dim3(grid_for((long long)H * nyp)), dim3(256), 0, st, zm.py.p, H, ny, nyp,
-                       y0, dy, z);
-    HIP_TRY(hipGetLastError());
-    RC(zm.end());
+    RC(zm.watch.begin(SLM_ZOOM_KERNEL_TABLES, st));
+    RC(launch_table(st, zm.px.p, 1, W, nx, nxp, nullptr, nullptr, x0, dx, z));
+    RC(launch_table(st, zm.py.p, 1, H, ny, nyp, nullptr, nullptr, y0, dy, z));
+    RC(zm.watch.end(st));
+    q.ain = ain ? zm.ain.p : nullptr;
+    q.levels = zm.levels.p;
+    q.px = zm.px.p;
+    q.py = zm.py.p;
+    q.field = zm.field.p;
+    q.r = zm.r.p;
+    q.partial = zm.partial.p;
 
     for (int b = 0; b < batch; ++b) {
         RC(slm::copy_sync(zm.holo.p, static_cast<const uint8_t*>(hologram) + (size_t)b * holo * el, holo * el,
                           hipMemcpyHostToDevice, st));
-        RC(zm.begin(SLM_ZOOM_KERNEL_FIELD));
-        hipLaunchKernelGGL(zoom_field_kernel, dim3(grid_for((long long)holo)), dim3(256), 0, st, zm.holo.p, kind,
-                           ain ? zm.ain.p : nullptr, zm.levels.p, zm.field.p, (long long)holo);
-        HIP_TRY(hipGetLastError());
-        RC(zm.end());
-        RC(zm.begin(SLM_ZOOM_KERNEL_ROWS));
-        const RowsParams rp{zm.field.p, zm.px.p, split_rows ? zm.partial.p : zm.r.p, H, W, nxp,
-                            split_rows ? kChunk : wchunks * kChunk};
-        const int sample_groups = (nxp / kTile + kWaves - 1) / kWaves;
-        hipLaunchKernelGGL(zoom_rows_kernel, dim3(sample_groups, row_tiles, split_rows ? wchunks : 1), dim3(kThreads),
-                           0, st, rp);
-        HIP_TRY(hipGetLastError());
-        if (split_rows) {
-            hipLaunchKernelGGL(zoom_rows_fold_kernel, dim3(grid_for((long long)H * nxp)), dim3(256), 0, st,
-                               zm.partial.p, zm.r.p, wchunks, (long long)H * nxp);
-            HIP_TRY(hipGetLastError());
-        }
-        RC(zm.end());
-        for (int j0 = 0; j0 < ny; j0 += band_rows) {
-            const int tile_rows = std::min(band_rows, nyp - j0), rows = std::min(band_rows, ny - j0);
-            RC(zm.begin(SLM_ZOOM_KERNEL_COLS));
-            const ColsParams cp{zm.py.p, zm.r.p, zm.partial.p, H, nyp, nxp, j0, band_rows};
-            hipLaunchKernelGGL(zoom_cols_kernel, dim3(sample_groups, tile_rows / kTile, chunks), dim3(kThreads), 0, st,
-                               cp);
-            HIP_TRY(hipGetLastError());
-            const FoldParams fp{zm.partial.p, zm.intensity.p, field ? zm.v.p : nullptr, chunks, band_rows, rows, nx,
-                                nxp};
-            hipLaunchKernelGGL(zoom_fold_kernel, dim3(grid_for((long long)rows * nx)), dim3(256), 0, st, fp);
-            HIP_TRY(hipGetLastError());
-            RC(zm.end());
-            const size_t at = ((size_t)b * ny + j0) * nx, n = (size_t)rows * nx;
-            RC(slm::copy_sync(intensity + at, zm.intensity.p, n * sizeof(float), hipMemcpyDeviceToHost, st));
-            if (field) RC(slm::copy_sync(field + 2 * at, zm.v.p, n * sizeof(double2), hipMemcpyDeviceToHost, st));
-        }
+        RC(enqueue_group(q, zm.holo.p, 0, 1, zm.intensity.p, field ? zm.v.p : nullptr, 0, true, nullptr,
+                         [&](int j0, int rows) {
+                             const size_t at = ((size_t)b * ny + j0) * nx, n = (size_t)rows * nx;
+                             RC(slm::copy_sync(intensity + at, zm.intensity.p, n * sizeof(float),
+                                               hipMemcpyDeviceToHost, st));
+                             if (field)
+                                 RC(slm::copy_sync(field + 2 * at, zm.v.p, n * sizeof(double2), hipMemcpyDeviceToHost,
+                                                   st));
+                             return 0;
+                         }));
     }
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
+}
+
+}  // namespace
+
+// ---- the resident zoom ----------------------------------------------------
+// Stream, buffers and tables stay with the handle; a run enqueues groups of
+// holograms back to back and returns, slm_zoom_read waits.
+struct slm_zoom {
+    int B = 0, H = 0, W = 0, max_ny = 0, max_nx = 0;
+    size_t cols_cap = kPartialBytes, rows_cap = kRowsPartialBytes;  // $SLM_ZOOM_PARTIAL_BYTES replaces both
+    hipStream_t stream = nullptr;
+    hipEvent_t frames_written = nullptr, frames_read = nullptr;  // the two orderings with a sequence's stream
+    hipEvent_t levels_landed = nullptr;                          // the last upload from level_host
+    DevBuf<float> ain;
+    DevBuf<double> mask, level_t, origins;  // origins: y0 [B], x0 [B], z [B]
+    DevBuf<float2> levels, px, py, field, r, partial;
+    DevBuf<uint8_t> holo;
+    DevBuf<float> intensity;
+    DevBuf<double2> v;
+    void* level_host = nullptr;  // pinned: float2 [256], then double [256]
+    double level_ct2pi = 0.0;    // what the level tables on the device were built for (0: nothing)
+    bool ain_set = false, mask_set = false, window_set = false, per_hologram = false, timed = false;
+    int ny = 0, nx = 0;
+    // the last run
+    bool ran = false, ran_field = false, ran_timed = false;
+    int ran_count = 0, ran_ny = 0, ran_nx = 0, groups = 0, bands = 0, split_launches = 0;
+    Stopwatch watch;
+};
+
+namespace {
+
+constexpr int kMaxBatch = 1024;
+// the field of one group, at most: with windows of a few tiles the partial caps alone would admit hundreds
+// of holograms of any size
+constexpr size_t kGroupFieldBytes = 1u << 30;
+
+void zoom_free(slm_zoom* zm) {
+    if (!zm) return;
+    if (zm->stream) (void)hipStreamSynchronize(zm->stream);
+    for (hipEvent_t e : {zm->frames_written, zm->frames_read, zm->levels_landed})
+        if (e) (void)hipEventDestroy(e);
+    if (zm->level_host) (void)hipHostFree(zm->level_host);
+    if (zm->stream) (void)hipStreamDestroy(zm->stream);
+    delete zm;
+}
+
+// holograms per group and the band of a run of `count`: as many holograms as keep the second product's
+// partials of the whole window within the cap (and the field within kGroupFieldBytes), spread evenly over
+// the groups; a window whose partials exceed the cap for one hologram runs hologram by hologram in bands
+void cut_run(const slm_zoom* zm, int count, int* group, int* band_rows) {
+    const int nyp = padded(zm->ny), nxp = padded(zm->nx);
+    const size_t whole = (size_t)((zm->H + kChunk - 1) / kChunk) * nyp * nxp * sizeof(float2);
+    size_t g = 1;
+    if (whole <= zm->cols_cap) {
+        g = std::min(zm->cols_cap / whole, std::max<size_t>(1, kGroupFieldBytes / ((size_t)zm->H * zm->W * 8)));
+        g = std::min<size_t>(g, count);
+        const size_t n_groups = (count + g - 1) / g;
+        g = (count + n_groups - 1) / n_groups;
+    }
+    *group = (int)g;
+    *band_rows = band_rows_for(zm->H, nyp, nxp, zm->cols_cap, (int)g);
+}
+
+// `count` holograms already on the device (levels or phases), on the handle's stream. `writer`, if not
+// null, is the stream that writes `dev_holo`: its later work waits for this run.
+int zoom_enqueue(slm_zoom* zm, const void* dev_holo, int kind, int count, double ct2pi, int want_field,
+                 hipStream_t writer) {
+    const hipStream_t st = zm->stream;
+    const int nxp = padded(zm->nx), nyp = padded(zm->ny);
+    const size_t holo = (size_t)zm->H * zm->W, el = kind == SLM_ZOOM_LEVELS_U8 ? 1 : sizeof(float);
+    const size_t window = (size_t)zm->ny * zm->nx;
+    zm->ran = false;
+    if (kind == SLM_ZOOM_LEVELS_U8 && ct2pi != zm->level_ct2pi) {
+        // the pinned tables are written only after their last upload has left them
+        HIP_TRY(hipEventSynchronize(zm->levels_landed));
+        float2* levels = static_cast<float2*>(zm->level_host);
+        double* level_t = reinterpret_cast<double*>(levels + 256);
+        level_tables(ct2pi, levels, level_t);
+        zm->level_ct2pi = 0.0;
+        HIP_TRY(hipMemcpyAsync(zm->levels.p, levels, 256 * sizeof(float2), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(zm->level_t.p, level_t, 256 * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipEventRecord(zm->levels_landed, st));
+        zm->level_ct2pi = ct2pi;
+    }
+    int group = 1, band_rows = kTile;
+    cut_run(zm, count, &group, &band_rows);
+    zm->watch.reset(zm->timed);
+    Pass q{st, &zm->watch, zm->H, zm->W, zm->ny, zm->nx, nyp, nxp, kind};
+    q.band_rows = band_rows;
+    q.rows_partial_bytes = zm->rows_cap;
+    q.px_stride = zm->per_hologram ? (size_t)zm->W * nxp : 0;
+    q.py_stride = zm->per_hologram ? (size_t)zm->H * nyp : 0;
+    const int last = count - (count - 1) / group * group;  // the last group's holograms
+    RC(zm->field.need((size_t)group * holo * sizeof(float2), st));
+    RC(zm->r.need((size_t)group * zm->H * nxp * sizeof(float2), st));
+    RC(zm->partial.need(std::max(partial_bytes(q, group), partial_bytes(q, last)), st));
+    RC(zm->intensity.need((size_t)count * window * sizeof(float), st));
+    if (want_field) RC(zm->v.need((size_t)count * window * sizeof(double2), st));
+    q.ain = zm->ain_set ? zm->ain.p : nullptr;
+    q.mask = zm->mask_set ? zm->mask.p : nullptr;
+    q.levels = zm->levels.p;
+    q.level_t = zm->level_t.p;
+    q.px = zm->px.p;
+    q.py = zm->py.p;
+    q.field = zm->field.p;
+    q.r = zm->r.p;
+    q.partial = zm->partial.p;
+
+    zm->groups = zm->split_launches = 0;
+    zm->bands = (zm->ny + band_rows - 1) / band_rows;
+    for (int first = 0; first < count; first += group, ++zm->groups) {
+        const int n = std::min(group, count - first);
+        RC(enqueue_group(q, static_cast<const uint8_t*>(dev_holo) + (size_t)first * holo * el, first, n,
+                         zm->intensity.p + (size_t)first * window, want_field ? zm->v.p + (size_t)first * window : nullptr,
+                         window, false, &zm->split_launches, [](int, int) { return 0; }));
+    }
+    if (writer) {
+        // the source's next write to its frames comes after this run's reads
+        HIP_TRY(hipEventRecord(zm->frames_read, st));
+        HIP_TRY(hipStreamWaitEvent(writer, zm->frames_read, 0));
+    }
+    zm->ran = true;
+    zm->ran_field = want_field != 0;
+    zm->ran_timed = zm->timed;
+    zm->ran_count = count;
+    zm->ran_ny = zm->ny;
+    zm->ran_nx = zm->nx;
+    return 0;
+}
+
+int check_run(const slm_zoom* zm, int kind, int count, double ct2pi) {
+    if (!zm) return fail(SLM_ERR_ARG, "null zoom handle");
+    RC(check_kind(kind));
+    if (count < 1 || count > zm->B)
+        return fail(SLM_ERR_ARG, "a run takes 1 .. %d holograms (the handle's batch), got %d", zm->B, count);
+    RC(check_ct2pi(kind, ct2pi));
+    if (!zm->window_set) return fail(SLM_ERR_STATE, "slm_zoom_run before slm_zoom_set_window");
+    return 0;
+}
+
+// holograms [first, first + count) of a sequence's frames, ordered after the chain that writes them
+int zoom_run_frames(slm_zoom* zm, const slm::SeqFrames& src, const char* what, int first, int count, double ct2pi,
+                    int want_field) {
+    if (!src.n) return fail(SLM_ERR_STATE, "%s before a sequence", what);
+    if (!src.frames) return fail(SLM_ERR_STATE, "the sequence was run without frames");
+    if (src.H != zm->H || src.W != zm->W)
+        return fail(SLM_ERR_ARG, "the frames are %d x %d, the zoom handle's holograms %d x %d", src.H, src.W, zm->H,
+                    zm->W);
+    if (first < 0 || count < 1 || first > src.n - count)
+        return fail(SLM_ERR_ARG, "frames %d .. %d lie outside the sequence's %d", first, first + count - 1, src.n);
+    RC(check_run(zm, SLM_ZOOM_LEVELS_U8, count, ct2pi));
+    RC(slm::ensure_device());
+    HIP_TRY(hipEventRecord(zm->frames_written, src.stream));
+    HIP_TRY(hipStreamWaitEvent(zm->stream, zm->frames_written, 0));
+    return zoom_enqueue(zm, src.frames + (size_t)first * zm->H * zm->W, SLM_ZOOM_LEVELS_U8, count, ct2pi, want_field,
+                        src.stream);
 }
 
 }  // namespace
@@ -439,17 +788,10 @@ int slm_farfield_zoom_timed(const void* hologram, int kind, int batch, int heigh
                             float* intensity, double* field, double* kernel_us) {
     RC(check_args(hologram, kind, batch, height, width, ain, ct2pi, y0, x0, dy, dx, ny, nx, z, intensity));
     RC(slm::ensure_device());
-    Zoom zm;
-    zm.timed = kernel_us != nullptr;
+    OneShot zm;
+    zm.watch.reset(kernel_us != nullptr);
     RC(zoom_run(zm, hologram, kind, batch, height, width, ain, ct2pi, y0, x0, dy, dx, ny, nx, z, intensity, field));
-    if (kernel_us) {
-        for (int c = 0; c < SLM_ZOOM_NUM_KERNEL_CLASSES; ++c) kernel_us[c] = 0.0;
-        for (size_t k = 0; k < zm.cls.size(); ++k) {
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, zm.ev[2 * k], zm.ev[2 * k + 1]));
-            kernel_us[zm.cls[k]] += 1e3 * ms;
-        }
-    }
+    if (kernel_us) RC(zm.watch.read(kernel_us));
     return 0;
 }
 
@@ -458,6 +800,168 @@ int slm_farfield_zoom(const void* hologram, int kind, int batch, int height, int
                       double* field) {
     return slm_farfield_zoom_timed(hologram, kind, batch, height, width, ain, ct2pi, y0, x0, dy, dx, ny, nx, z,
                                    intensity, field, nullptr);
+}
+
+int slm_zoom_create(int batch, int height, int width, int max_ny, int max_nx, slm_zoom** out) {
+    if (!out) return fail(SLM_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (batch < 1 || batch > kMaxBatch)
+        return fail(SLM_ERR_ARG, "a zoom handle takes 1 .. %d holograms per run, got %d", kMaxBatch, batch);
+    RC(check_sides(height, width));
+    RC(check_samples(max_ny, max_nx));
+    size_t cap = 0;
+    if (const char* env = std::getenv("SLM_ZOOM_PARTIAL_BYTES")) {
+        char* end = nullptr;
+        const long long v = std::strtoll(env, &end, 10);
+        if (end == env || *end || v < 1)
+            return fail(SLM_ERR_ARG, "$SLM_ZOOM_PARTIAL_BYTES must be a positive whole number, got \"%s\"", env);
+        cap = (size_t)v;
+    }
+    RC(slm::ensure_device());
+    slm_zoom* zm = new slm_zoom;
+    zm->B = batch;
+    zm->H = height;
+    zm->W = width;
+    zm->max_ny = max_ny;
+    zm->max_nx = max_nx;
+    if (cap) zm->cols_cap = zm->rows_cap = cap;
+    int rc = [&]() {
+        HIP_TRY(hipStreamCreateWithFlags(&zm->stream, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&zm->frames_written, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&zm->frames_read, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&zm->levels_landed, hipEventDisableTiming));
+        HIP_TRY(hipHostMalloc(&zm->level_host, 256 * (sizeof(float2) + sizeof(double)), hipHostMallocDefault));
+        RC(zm->levels.need(256 * sizeof(float2), zm->stream));
+        RC(zm->level_t.need(256 * sizeof(double), zm->stream));
+        return 0;
+    }();
+    if (rc) {
+        zoom_free(zm);
+        return rc;
+    }
+    *out = zm;
+    return 0;
+}
+
+int slm_zoom_destroy(slm_zoom* zm) {
+    if (zm) (void)slm::ensure_device();
+    zoom_free(zm);
+    return 0;
+}
+
+int slm_zoom_set_ain(slm_zoom* zm, const float* ain) {
+    if (!zm) return fail(SLM_ERR_ARG, "null zoom handle");
+    const size_t holo = (size_t)zm->H * zm->W;
+    RC(check_ain(ain, holo));
+    RC(slm::ensure_device());
+    zm->ain_set = false;
+    if (!ain) return 0;
+    RC(zm->ain.need(holo * sizeof(float), zm->stream));
+    RC(slm::copy_sync(zm->ain.p, ain, holo * sizeof(float), hipMemcpyHostToDevice, zm->stream));
+    zm->ain_set = true;
+    return 0;
+}
+
+int slm_zoom_set_mask(slm_zoom* zm, const double* mask) {
+    if (!zm) return fail(SLM_ERR_ARG, "null zoom handle");
+    const size_t holo = (size_t)zm->H * zm->W;
+    for (size_t i = 0; mask && i < holo; ++i)
+        if (!std::isfinite(mask[i])) return fail(SLM_ERR_ARG, "the mask has a non-finite entry");
+    RC(slm::ensure_device());
+    zm->mask_set = false;
+    if (!mask) return 0;
+    RC(zm->mask.need(holo * sizeof(double), zm->stream));
+    RC(slm::copy_sync(zm->mask.p, mask, holo * sizeof(double), hipMemcpyHostToDevice, zm->stream));
+    zm->mask_set = true;
+    return 0;
+}
+
+int slm_zoom_set_window(slm_zoom* zm, int per_hologram, const double* y0, const double* x0, const double* z,
+                        double dy, double dx, int ny, int nx) {
+    if (!zm || !y0 || !x0 || !z) return fail(SLM_ERR_ARG, "null argument");
+    RC(check_samples(ny, nx));
+    if (ny > zm->max_ny || nx > zm->max_nx)
+        return fail(SLM_ERR_ARG, "a window of %d x %d samples exceeds the handle's %d x %d", ny, nx, zm->max_ny,
+                    zm->max_nx);
+    const int windows = per_hologram ? zm->B : 1;
+    bool finite = std::isfinite(dy) && std::isfinite(dx);
+    for (int i = 0; i < windows; ++i) finite = finite && std::isfinite(y0[i]) && std::isfinite(x0[i]) && std::isfinite(z[i]);
+    if (!finite) return fail(SLM_ERR_ARG, "%s", kNotFinite);
+    RC(check_pitch(dy, dx));
+    RC(slm::ensure_device());
+    const hipStream_t st = zm->stream;
+    const int nxp = padded(nx), nyp = padded(ny);
+    zm->window_set = false;
+    RC(zm->px.need((size_t)windows * zm->W * nxp * sizeof(float2), st));
+    RC(zm->py.need((size_t)windows * zm->H * nyp * sizeof(float2), st));
+    const double *dev_y0 = nullptr, *dev_x0 = nullptr, *dev_z = nullptr;
+    if (per_hologram) {
+        RC(zm->origins.need(3 * (size_t)windows * sizeof(double), st));
+        dev_y0 = zm->origins.p;
+        dev_x0 = dev_y0 + windows;
+        dev_z = dev_x0 + windows;
+        const size_t bytes = (size_t)windows * sizeof(double);
+        RC(slm::copy_sync(zm->origins.p, y0, bytes, hipMemcpyHostToDevice, st));
+        RC(slm::copy_sync(zm->origins.p + windows, x0, bytes, hipMemcpyHostToDevice, st));
+        RC(slm::copy_sync(zm->origins.p + 2 * windows, z, bytes, hipMemcpyHostToDevice, st));
+    }
+    RC(launch_table(st, zm->px.p, windows, zm->W, nx, nxp, dev_x0, dev_z, x0[0], dx, z[0]));
+    RC(launch_table(st, zm->py.p, windows, zm->H, ny, nyp, dev_y0, dev_z, y0[0], dy, z[0]));
+    zm->per_hologram = per_hologram != 0;
+    zm->ny = ny;
+    zm->nx = nx;
+    zm->window_set = true;
+    return 0;
+}
+
+int slm_zoom_set_timed(slm_zoom* zm, int timed) {
+    if (!zm) return fail(SLM_ERR_ARG, "null zoom handle");
+    zm->timed = timed != 0;
+    return 0;
+}
+
+int slm_zoom_run(slm_zoom* zm, const void* hologram, int kind, int count, double ct2pi, int want_field) {
+    RC(check_run(zm, kind, count, ct2pi));
+    if (!hologram) return fail(SLM_ERR_ARG, "null argument");
+    RC(slm::ensure_device());
+    const size_t bytes = (size_t)count * zm->H * zm->W * (kind == SLM_ZOOM_LEVELS_U8 ? 1 : sizeof(float));
+    zm->ran = false;
+    RC(zm->holo.need(bytes, zm->stream));
+    HIP_TRY(hipMemcpyAsync(zm->holo.p, hologram, bytes, hipMemcpyHostToDevice, zm->stream));
+    return zoom_enqueue(zm, zm->holo.p, kind, count, ct2pi, want_field, nullptr);
+}
+
+int slm_zoom_run_spots(slm_zoom* zm, slm_spots* sp, int first, int count, double ct2pi, int want_field) {
+    if (!zm || !sp) return fail(SLM_ERR_ARG, "null argument");
+    return zoom_run_frames(zm, slm::spots_seq_frames(sp), "slm_zoom_run_spots", first, count, ct2pi, want_field);
+}
+
+int slm_zoom_run_plan(slm_zoom* zm, slm_plan* plan, int first, int count, double ct2pi, int want_field) {
+    if (!zm || !plan) return fail(SLM_ERR_ARG, "null argument");
+    return zoom_run_frames(zm, slm::plan_seq_frames(plan), "slm_zoom_run_plan", first, count, ct2pi, want_field);
+}
+
+int slm_zoom_read(slm_zoom* zm, float* intensity, double* field, double* kernel_us) {
+    if (!zm) return fail(SLM_ERR_ARG, "null zoom handle");
+    if (!zm->ran) return fail(SLM_ERR_STATE, "slm_zoom_read before a run");
+    if (field && !zm->ran_field) return fail(SLM_ERR_STATE, "the run was not asked for the field");
+    if (kernel_us && !zm->ran_timed) return fail(SLM_ERR_STATE, "the run was not timed (slm_zoom_set_timed)");
+    RC(slm::ensure_device());
+    HIP_TRY(hipStreamSynchronize(zm->stream));
+    const size_t n = (size_t)zm->ran_count * zm->ran_ny * zm->ran_nx;
+    if (intensity) RC(slm::copy_sync(intensity, zm->intensity.p, n * sizeof(float), hipMemcpyDeviceToHost, zm->stream));
+    if (field) RC(slm::copy_sync(field, zm->v.p, n * sizeof(double2), hipMemcpyDeviceToHost, zm->stream));
+    if (kernel_us) RC(zm->watch.read(kernel_us));
+    return 0;
+}
+
+int slm_zoom_info(slm_zoom* zm, int* info) {
+    if (!zm || !info) return fail(SLM_ERR_ARG, "null argument");
+    if (!zm->ran) return fail(SLM_ERR_STATE, "slm_zoom_info before a run");
+    info[0] = zm->groups;
+    info[1] = zm->bands;
+    info[2] = zm->split_launches;
+    return 0;
 }
 
 }  // extern "C"

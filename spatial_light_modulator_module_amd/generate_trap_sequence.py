@@ -3,7 +3,7 @@ of traps at fractional positions, one chain on the device per trajectory.
 
     python -m spatial_light_modulator_module_amd.generate_trap_sequence <name> -v V -ct2pi N [-loops 4] [-first 30]
         [-tol 0] [--feedback 1] [--shape 1080x1920] [-ii PATH] [-p]
-        [--expected [--oversample 8] [--margin 4] [--expected_z 0]]
+        [--expected [--follow] [--oversample 8] [--margin 4] [--expected_z 0]]
 
 The reference reaches moving traps in two steps: generate_traps_image_sequence.py
 rasterises the positions into images (whole pixels), generate_hologram_sequence.py
@@ -23,8 +23,11 @@ field those uint8 frames produce is written too, as
 ``images/moving_traps/<name>_<V>_expected/<i>.png``: one window for the whole
 trajectory (move_traps.trap_window: every position +- ``--margin`` far-field
 pixels, ``--oversample`` samples per pixel, in the plane of ``--expected_z``),
-all frames through one move_traps.expected_outcome call, each image scaled to
-its own brightest sample. Single GPU only.
+or with ``--follow`` one window per frame around that frame's traps, all of one
+size (move_traps.trap_windows). The frames do not leave the device for it: they
+are previewed where the sequence left them (trap_array_sequence's ``expected``,
+the resident zoom), each image scaled to its own brightest sample. Single GPU
+only.
 """
 from __future__ import annotations
 
@@ -78,9 +81,13 @@ def generate_trap_sequence(args):
     if args.preview:
         os.makedirs(dest_preview, exist_ok=True)
     ain = incoming_amplitude(args, args.shape)
+    expected = None
+    if args.expected:
+        expected = dict(margin=args.margin, oversample=args.oversample, z=args.expected_z,
+                        follow=getattr(args, "follow", False))
     res = move_traps.trap_array_sequence(args.shape, ys, xs, zs, inten, loops_first=args.first, loops=args.max_loops,
                                          tol=args.tolerance, feedback=args.feedback, ain=ain,
-                                         ct2pi=args.correspond_to2pi, holograms=True)
+                                         ct2pi=args.correspond_to2pi, holograms=True, expected=expected)
     curves = []
     for i in range(len(res.frames)):
         sys.stdout.write(f"\rcreating {i}. hologram ")
@@ -91,21 +98,18 @@ def generate_trap_sequence(args):
             Image.fromarray(res.frames[i]).save(f"{dest_preview}/{i}.png")
         curves.append([float(u) for u in res.stats[i][:int(res.iters[i]), 1]])
     if args.expected:
-        write_expected(args, res.frames, ys, xs, ain)
+        write_expected(args, res.expected)
     return curves
 
 
-def write_expected(args, frames, ys, xs, ain):
-    """--expected: what the uint8 frames produce, one zoomed far field for all
-    of them on the window of the whole trajectory, each written as an 8-bit
-    image scaled to its own brightest sample."""
+def write_expected(args, inten):
+    """--expected: what the uint8 frames produce (the zoomed far field
+    trap_array_sequence computed from them on the device), each written as an
+    8-bit image scaled to its own brightest sample."""
     from PIL import Image
 
     dest = expected_dir(args.name, args.version)
     os.makedirs(dest, exist_ok=True)
-    window = move_traps.trap_window(ys, xs, margin=args.margin, oversample=args.oversample)
-    inten = move_traps.expected_outcome(np.ascontiguousarray(frames), window, z=args.expected_z, ain=ain,
-                                        ct2pi=args.correspond_to2pi)
     for i, img in enumerate(inten.astype(np.float64)):
         peak = img.max() or 1.0  # a dark frame stays dark
         Image.fromarray(np.floor(255.0 * img / peak).astype(np.uint8)).save(f"{dest}/{i}.png")  # uint8 2-D: mode L
@@ -133,6 +137,8 @@ def build_parser():
     p.add_argument("-p", "--preview", action="store_true", help="also write the quantised frames as images")
     p.add_argument("--expected", action="store_true",
                    help="also write the far field each quantised frame produces around the traps, as images")
+    p.add_argument("--follow", action="store_true",
+                   help="--expected: one window per frame around that frame's traps instead of one for the trajectory")
     p.add_argument("--oversample", metavar="INT", default=8, type=int,
                    help="--expected: samples per far-field pixel")
     p.add_argument("--margin", metavar="PX", default=4.0, type=float,

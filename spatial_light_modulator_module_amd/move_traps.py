@@ -28,6 +28,11 @@ DESIGN.md section 7).
   of trap positions, sampled between the FFT bins in a chosen focal plane
   (slm_farfield_zoom). What show_expected_outcome's |fft2|^2 cannot show of a
   trap at a fractional position.
+* ``trap_windows`` / ``trap_array_sequence(expected=...)`` — the same preview
+  for every frame of a trajectory, from the uint8 frames where the sequence
+  left them on the device (the resident zoom, slm_zoom_*): one window for the
+  trajectory or one per frame that follows the traps, the sequence's
+  correction mask taken off if asked.
 """
 from __future__ import annotations
 
@@ -103,8 +108,30 @@ def _get_spots(batch, h, w, n_traps, has_ain, loops) -> _lib.Spots:
 
 
 def clear_spots() -> None:
+    """Closes the cached Spots handles, and the zoom handles that preview their frames."""
+    while _ZOOMS:
+        _ZOOMS.popitem()[1].close()
     while _SPOTS:
         _SPOTS.popitem()[1].close()
+
+
+# resident zoom handles of trap_array_sequence(expected=...), per (frames per run, H, W)
+_ZOOMS: "collections.OrderedDict[tuple, _lib.Zoom]" = collections.OrderedDict()
+_MAX_ZOOMS = 2
+
+
+def _get_zoom(count, h, w, size) -> _lib.Zoom:
+    key = (count, h, w)
+    zm = _ZOOMS.pop(key, None)
+    if zm is not None and (zm.max_size[0] < size[0] or zm.max_size[1] < size[1]):
+        zm.close()
+        zm = None
+    if zm is None:
+        while len(_ZOOMS) >= _MAX_ZOOMS:
+            _ZOOMS.popitem(last=False)[1].close()
+        zm = _lib.Zoom(count, h, w, size)
+    _ZOOMS[key] = zm
+    return zm
 
 
 def lens_to_z(focal_length: float) -> float:
@@ -163,11 +190,57 @@ def trap_array_frame(shape, ys, xs, zs=None, intensity=None, loops=30, feedback=
     return holo, frame, inten, stats, weights
 
 
-SequenceResult = collections.namedtuple("SequenceResult", "frames holograms intensities stats iters weights")
+SequenceResult = collections.namedtuple("SequenceResult", "frames holograms intensities stats iters weights expected",
+                                        defaults=(None,))
 SequenceResult.__doc__ = """What trap_array_sequence returns, every field with a leading [F] (one
 trajectory) or [F][B] (a batch): frames uint8 [H][W], holograms float64 [H][W]
 or None, intensities |V_m|^2 [M], stats [max(loops_first, loops)][4] (rows past
-iters are 0), iters (iterations each frame ran), weights [M]."""
+iters are 0), iters (iterations each frame ran), weights [M], expected float32
+[ny][nx] (the zoomed far field of each frame) or None."""
+
+
+def _expected_options(expected, ys, xs):
+    """trap_array_sequence's expected=dict(...) as (origins [F][2] or one (y0, x0),
+    pitch, size, z, mask_off); ValueError on anything it cannot take."""
+    if not isinstance(expected, dict):
+        raise ValueError(f"expected is a dict of margin, oversample, z, follow and mask_off, got {expected!r}")
+    unknown = set(expected) - {"margin", "oversample", "z", "follow", "mask_off"}
+    if unknown:
+        raise ValueError(f"expected has unknown keys {sorted(unknown)}")
+    z = float(expected.get("z", 0.0))
+    if not np.isfinite(z):
+        raise ValueError(f"expected: z must be finite, got {z}")
+    margin, oversample = expected.get("margin", 4.0), expected.get("oversample", 8)
+    if expected.get("follow", False):
+        origins, pitch, size = trap_windows(ys.reshape(ys.shape[0], -1), xs.reshape(xs.shape[0], -1), margin,
+                                            oversample)
+    else:
+        origins, pitch, size = trap_window(ys, xs, margin, oversample)
+    return origins, pitch, size, z, bool(expected.get("mask_off", False))
+
+
+def _expected_from_device(sp, b, h, w, f, options, ain, mask, ct2pi):
+    """The zoomed far field [F][B][ny][nx] of the frames the sequence left on the
+    device, through a cached resident zoom handle: at most 1024 frames per run,
+    a per-frame window (the same for a frame's B holograms) when following."""
+    origins, pitch, size, z, mask_off = options
+    total = f * b
+    per_run = min(total, _lib.ZOOM_MAX_BATCH)
+    zm = _get_zoom(per_run, h, w, size)
+    zm.set_ain(ain)
+    zm.set_mask(mask if mask_off else None)
+    follow = np.ndim(origins) == 2
+    if not follow:
+        zm.set_window(origins, pitch, size, z)
+    out = np.empty((total,) + tuple(size), np.float32)
+    for first in range(0, total, per_run):
+        count = min(per_run, total - first)
+        if follow:
+            o = np.repeat(np.asarray(origins, np.float64), b, axis=0)[first:first + count]
+            zm.set_window(np.concatenate([o, np.repeat(o[-1:], per_run - count, axis=0)]), pitch, size, z)
+        zm.run_spots(sp, first, count, ct2pi)
+        out[first:first + count] = zm.read()
+    return out.reshape((f, b) + tuple(size))
 
 
 def _sequence_arrays(ys, xs, zs, intensity, initial_weights):
@@ -204,7 +277,7 @@ def _sequence_arrays(ys, xs, zs, intensity, initial_weights):
 
 def trap_array_sequence(shape, ys, xs, zs=None, intensity=None, loops_first=30, loops=4, tol=0.0, feedback=1.0,
                         ain=None, initial_phase=None, initial_weights=None, mask=None, mask_flag: bool = True,
-                        ct2pi=256, holograms=False, resume=False) -> SequenceResult:
+                        ct2pi=256, holograms=False, resume=False, expected=None) -> SequenceResult:
     """A trajectory of a trap list as one chain on the device
     (slm_spots_sequence): ys, xs, zs, intensity are [F][M], or [F][B][M] for B
     trajectories at once; trap m of frame f is trap m of frame f-1, moved.
@@ -217,10 +290,18 @@ def trap_array_sequence(shape, ys, xs, zs=None, intensity=None, loops_first=30, 
     shape and trap count: its frame 0 is an ordinary later frame, feedback and
     a_in stay the handle's, and initial_phase / initial_weights must be None.
     Returns a SequenceResult; holograms (float64, as update_hologram's) only
-    with holograms=True."""
+    with holograms=True. expected=dict(margin=4.0, oversample=8, z=0.0,
+    follow=False, mask_off=False) adds result.expected, the zoomed far field of
+    every uint8 frame (as expected_outcome gives it, bit for bit when no mask is
+    taken off), computed from the frames where the sequence left them on the
+    device: on the whole trajectory's trap_window, or with follow=True on each
+    frame's own window of trap_windows (one common size); mask_off=True takes
+    the sequence's own mask off again, so that the preview shows the traps and
+    not the aberration the mask is there to cancel."""
     h, w = int(shape[0]), int(shape[1])
     y, x, z, inten, w0, single = _sequence_arrays(ys, xs, zs, intensity, initial_weights)
     f, b, m = y.shape
+    options = None if expected is None else _expected_options(expected, y, x)
     if initial_phase is not None and np.size(initial_phase) != b * h * w:
         raise ValueError(f"initial_phase has {np.size(initial_phase)} entries, {b} holograms of {h} x {w} need "
                          f"{b * h * w}")
@@ -251,10 +332,13 @@ def trap_array_sequence(shape, ys, xs, zs=None, intensity=None, loops_first=30, 
     frames, phases, v, stats, weights, iters = sp.sequence_read(phases=bool(holograms))
     holo = phases.astype(np.float64) if holograms else None
     inten_out = v.real ** 2 + v.imag ** 2
+    exp = None
+    if options is not None:
+        exp = _expected_from_device(sp, b, h, w, f, options, ain, mask if use_mask else None, ct2pi)
     if single:
         return SequenceResult(frames[:, 0], None if holo is None else holo[:, 0], inten_out[:, 0], stats[:, 0],
-                              iters[:, 0], weights[:, 0])
-    return SequenceResult(frames, holo, inten_out, stats, iters, weights)
+                              iters[:, 0], weights[:, 0], None if exp is None else exp[:, 0])
+    return SequenceResult(frames, holo, inten_out, stats, iters, weights, exp)
 
 
 def trap_window(ys, xs, margin=4.0, oversample=8):
@@ -284,6 +368,21 @@ def trap_window(ys, xs, margin=4.0, oversample=8):
         origin.append(first / oversample)
         size.append(n)
     return (origin[0], origin[1]), (1.0 / oversample, 1.0 / oversample), (size[0], size[1])
+
+
+def trap_windows(ys, xs, margin=4.0, oversample=8):
+    """A window per frame of a trajectory ys, xs [F][M] that follows the traps:
+    frame f gets trap_window's box around its own traps, the origin snapped to
+    the pitch as there, and all frames share the largest size among them (a
+    smaller frame's window grows at its far edges). Returns (origins [F][2],
+    pitch, size). Pure host code."""
+    y, x = np.asarray(ys, dtype=np.float64), np.asarray(xs, dtype=np.float64)
+    if y.ndim != 2 or y.shape != x.shape or y.size == 0:
+        raise ValueError(f"a trajectory is ys, xs [F][M], got shapes {y.shape} and {x.shape}")
+    boxes = [trap_window(y[f], x[f], margin, oversample) for f in range(y.shape[0])]
+    origins = np.array([box[0] for box in boxes], dtype=np.float64)
+    size = (max(box[2][0] for box in boxes), max(box[2][1] for box in boxes))
+    return origins, boxes[0][1], size
 
 
 def expected_outcome(hologram_or_frame, window, z=0.0, ain=None, ct2pi=None):
