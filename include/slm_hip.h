@@ -562,17 +562,23 @@ int slm_spots_superpose(int batch, int height, int width, int n_traps, const dou
  * complex64 once. No atomics: results are bitwise reproducible, do not depend
  * on the batch, and a sample's value depends on its position alone, not on the
  * window around it.
- * slm_farfield_zoom: one-shot, host pointers in and out; the batch shares the
+ * slm_farfield_zoom: one-shot, host pointers in and out: a resident zoom (below)
+ *   of one hologram, created and destroyed by the call. The batch shares the
  *   window and ain [h][w] (NULL = ones) and runs hologram by hologram;
  *   intensity [batch][ny][nx] float32; field [batch][ny][nx][2] = V from the
  *   float64 fold, or NULL. It synchronises and frees its buffers before it
- *   returns. SLM_ERR_ARG: a null hologram or intensity, an unknown kind,
+ *   returns; while it runs it holds one hologram's whole window on the device
+ *   (at 4096 x 4096 samples 64 MB of intensity and, with the field, 256 MB
+ *   more). Its caps on the partial buffers are the built-in ones: it does not
+ *   read $SLM_ZOOM_PARTIAL_BYTES. Every argument is checked before anything is
+ *   created on the device. SLM_ERR_ARG: a null hologram or intensity, an unknown kind,
  *   batch < 1, a side outside 2 .. 4096, ny or nx outside 1 .. 4096, y0, x0, dy,
  *   dx or z not finite, dy or dx <= 0, ct2pi not finite or <= 0 with levels, a
  *   non-finite a_in entry, a_in zero everywhere.
  * slm_farfield_zoom_timed: the same; kernel_us[SLM_ZOOM_NUM_KERNEL_CLASSES]
  *   (NULL = untimed) receives the microseconds HIP events measured around the
- *   kernels of each class, summed over the holograms; copies are excluded.    */
+ *   kernels of each class, summed over the holograms (the two table launches
+ *   once per call); copies are excluded.                                      */
 #define SLM_ZOOM_PHASE_F32 0
 #define SLM_ZOOM_LEVELS_U8 1
 #define SLM_ZOOM_KERNEL_TABLES 0 /* zoom_table_kernel: Px and Py, once per call */
@@ -588,8 +594,9 @@ int slm_farfield_zoom_timed(const void* hologram, int kind, int batch, int heigh
                             float* intensity, double* field, double* kernel_us);
 
 /* ---- resident zoom: the zoomed far field with stream, buffers and tables kept --
- * The same far field on a handle that keeps what the one-shot creates and frees
- * per call, runs all holograms of a call in the same launches (in groups that
+ * The same far field on a handle, the one host path of the kernels (the one-shot
+ * above creates such a handle for one hologram and destroys it again). It keeps
+ * stream, buffers and tables, runs all holograms of a call in the same launches (in groups that
  * bound the work buffers), gives each hologram a window of its own if asked,
  * takes a correction mask off, and reads the uint8 frames of the last trap or
  * image sequence where they already are, on the device. Without a mask a
@@ -605,7 +612,8 @@ int slm_farfield_zoom_timed(const void* hologram, int kind, int batch, int heigh
  * of arg rounded to complex64, times a_in as before.
  * slm_zoom_create: `batch` (1 .. 1024) holograms per run at most, sides as the
  *   one-shot, windows of up to max_ny x max_nx (1 .. 4096) samples. Creates the
- *   stream; buffers are sized at need, only grow, and go with the handle.
+ *   stream; buffers are sized at need (the level tables at the first run on
+ *   levels), only grow, and go with the handle.
  *   $SLM_ZOOM_PARTIAL_BYTES (a positive whole number, read here) replaces the two
  *   caps of the partial buffers (64 MB for the second product, 128 MB for the
  *   split first product); anything else in it gives SLM_ERR_ARG.

@@ -198,11 +198,10 @@ std::mutex g_frames_mu;
 Scratch g_in, g_mask, g_out, g_phase, g_coords;
 hipStream_t g_frames_stream = nullptr;
 
-int grid_for(long long n) { return (int)std::min<long long>(8192, (n + 255) / 256); }
-
 }  // namespace
 
 using slm::fail;
+using slm::grid_for;
 
 namespace slm {
 

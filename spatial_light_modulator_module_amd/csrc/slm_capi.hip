@@ -1080,14 +1080,7 @@ int slm_plan_sequence(slm_plan* p, int n_frames, const void* targets, const uint
     RC(engine_of(p, &e));
     PlanState& s = p->s;
     SeqState& q = p->seq;
-    if (n_frames < 1) return fail(SLM_ERR_ARG, "%d frames: a sequence has at least one", n_frames);
-    if (loops_first < 1 || loops_first > s.max_loops || loops < 1 || loops > s.max_loops)
-        return fail(SLM_ERR_ARG, "loops_first %d and loops %d must lie in 1 .. max_loops %d", loops_first, loops,
-                    s.max_loops);
-    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(SLM_ERR_ARG, "tol must be finite and >= 0, got %g", tol);
-    if (rule != SLM_QUANT_ASTYPE && rule != SLM_QUANT_PIL) return fail(SLM_ERR_ARG, "unknown rule %d", rule);
-    if (!(ct2pi > 0.0) || !std::isfinite(ct2pi))
-        return fail(SLM_ERR_ARG, "ct2pi must be finite and positive, got %g", ct2pi);
+    RC(slm::check_sequence_args(n_frames, loops_first, loops, s.max_loops, tol, rule, ct2pi));
     const bool mraf = s.algo == SLM_ALGO_MRAF;
     if (!gs_like(s.algo)) return fail(SLM_ERR_STATE, "sequences run on GS, weighted-GS and MRAF plans, not on GD plans");
     if (s.has_ain && !p->ain_set) return fail(SLM_ERR_STATE, "slm_plan_sequence before slm_plan_set_ain");

@@ -461,13 +461,14 @@ __global__ void __launch_bounds__(kFieldsThreads) spot_superpose_kernel(Superpos
     }
 }
 
-int grid_for(long long n) { return (int)std::min<long long>(8192, (n + 255) / 256); }
 int padded_traps(int m) { return (m + kTile - 1) / kTile * kTile; }
 
 }  // namespace
 
 using slm::DevBuf;
 using slm::fail;
+using slm::grid_for;
+using slm::Stopwatch;
 
 struct slm_spots {
     int B = 0, H = 0, W = 0, max_traps = 0, has_ain = 0, max_loops = 0;
@@ -679,45 +680,20 @@ int default_start(slm_spots* s) {
     return 0;
 }
 
-struct Timer {
-    std::vector<hipEvent_t> ev;
-    std::vector<int> cls;
-    hipStream_t st;
-    bool on;
-    int begin(int c) {
-        if (!on) return 0;
-        hipEvent_t a = nullptr, b = nullptr;
-        HIP_TRY(hipEventCreate(&a));
-        ev.push_back(a);
-        HIP_TRY(hipEventCreate(&b));
-        ev.push_back(b);
-        cls.push_back(c);
-        HIP_TRY(hipEventRecord(a, st));
-        return 0;
-    }
-    int end() {
-        if (!on) return 0;
-        HIP_TRY(hipEventRecord(ev.back(), st));
-        return 0;
-    }
-    ~Timer() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-};
-
 // one frame: fr.loops iterations of fields, update and superposition; the first reads `start`,
 // the others the state the one before left
-int run_frame(slm_spots* s, const Frame& fr, const float2* start, Timer& tm) {
+int run_frame(slm_spots* s, const Frame& fr, const float2* start, Stopwatch& tm) {
+    const hipStream_t st = s->stream;
     for (int it = 0; it < fr.loops; ++it) {
-        RC(tm.begin(SLM_SPOTS_KERNEL_FIELDS));
+        RC(tm.begin(SLM_SPOTS_KERNEL_FIELDS, st));
         RC(launch_fields(s, it == 0 ? start : s->u.p, fr.stop));
-        RC(tm.end());
-        RC(tm.begin(SLM_SPOTS_KERNEL_UPDATE));
+        RC(tm.end(st));
+        RC(tm.begin(SLM_SPOTS_KERNEL_UPDATE, st));
         RC(launch_update(s, fr, it));
-        RC(tm.end());
-        RC(tm.begin(SLM_SPOTS_KERNEL_SUPERPOSE));
+        RC(tm.end(st));
+        RC(tm.begin(SLM_SPOTS_KERNEL_SUPERPOSE, st));
         RC(launch_superpose(s, fr, it, s->c.p, s->u.p));
-        RC(tm.end());
+        RC(tm.end(st));
     }
     return 0;
 }
@@ -731,20 +707,14 @@ int run_loops(slm_spots* s, int loops, double* us_per_class) {
     RC(slm::ensure_device());
     s->seq_resumable = false;  // the run overwrites the unit field a sequence left
     RC(default_start(s));
-    Timer tm{{}, {}, s->stream, us_per_class != nullptr};
+    Stopwatch tm;
+    tm.reset(us_per_class != nullptr);
     RC(run_frame(s, own_frame(s, loops), s->u0.p, tm));
     s->has_run = true;
     s->last_loops = loops;
-    if (us_per_class) {
-        HIP_TRY(hipStreamSynchronize(s->stream));
-        for (int k = 0; k < SLM_SPOTS_NUM_KERNEL_CLASSES; ++k) us_per_class[k] = 0.0;
-        for (size_t k = 0; k < tm.cls.size(); ++k) {
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, tm.ev[2 * k], tm.ev[2 * k + 1]));
-            us_per_class[tm.cls[k]] += 1e3 * ms;
-        }
-    }
-    return 0;
+    if (!us_per_class) return 0;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return tm.read(us_per_class, SLM_SPOTS_NUM_KERNEL_CLASSES);
 }
 
 // how the fields product is cut for Mp: a function of the shape and the list alone, never of the batch
@@ -859,11 +829,7 @@ int slm_spots_set_ain(slm_spots* s, const float* ain) {
     if (!s->has_ain) return fail(SLM_ERR_STATE, "the handle was created without a_in");
     const size_t holo = (size_t)s->H * s->W;
     double sum = 0.0;
-    for (size_t i = 0; i < holo; ++i) {
-        if (!std::isfinite(ain[i])) return fail(SLM_ERR_ARG, "a_in has a non-finite entry");
-        sum += (double)ain[i] * (double)ain[i];
-    }
-    if (!(sum > 0.0)) return fail(SLM_ERR_ARG, "a_in is zero everywhere");
+    RC(slm::check_ain(ain, holo, &sum));
     RC(slm::ensure_device());
     s->seq_resumable = false;
     RC(up(s, s->ain.p, ain, holo * sizeof(float)));
@@ -936,16 +902,9 @@ int slm_spots_sequence(slm_spots* s, int n_frames, int n_traps, const double* ys
                        const float* intensity, const float* weights0, int loops_first, int loops, double tol,
                        int resume, const double* mask, double ct2pi, int rule, int want_frames, int want_phases) {
     if (!s || !ys || !xs) return fail(SLM_ERR_ARG, "null argument");
-    if (n_frames < 1) return fail(SLM_ERR_ARG, "%d frames: a sequence has at least one", n_frames);
     if (n_traps < 1 || n_traps > s->max_traps)
         return fail(SLM_ERR_ARG, "%d traps outside 1 .. max_traps %d", n_traps, s->max_traps);
-    if (loops_first < 1 || loops_first > s->max_loops || loops < 1 || loops > s->max_loops)
-        return fail(SLM_ERR_ARG, "loops_first %d and loops %d must lie in 1 .. max_loops %d", loops_first, loops,
-                    s->max_loops);
-    if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(SLM_ERR_ARG, "tol must be finite and >= 0, got %g", tol);
-    if (rule != SLM_QUANT_ASTYPE && rule != SLM_QUANT_PIL) return fail(SLM_ERR_ARG, "unknown rule %d", rule);
-    if (!(ct2pi > 0.0) || !std::isfinite(ct2pi))
-        return fail(SLM_ERR_ARG, "ct2pi must be finite and positive, got %g", ct2pi);
+    RC(slm::check_sequence_args(n_frames, loops_first, loops, s->max_loops, tol, rule, ct2pi));
     if (resume && weights0) return fail(SLM_ERR_ARG, "a resumed sequence takes its weights from the previous one");
     const size_t bm_in = (size_t)s->B * n_traps, n = (size_t)n_frames * bm_in;
     RC(check_traps(n, ys, xs, zs, intensity));
@@ -992,7 +951,7 @@ int slm_spots_sequence(slm_spots* s, int n_frames, int n_traps, const double* ys
     HIP_TRY(hipMemsetAsync(s->seq_stats.p, 0, F * s->B * stats_loops * 4 * sizeof(double), s->stream));
 
     // ---- the chain: per frame one table launch, then its iterations ----
-    Timer untimed{{}, {}, s->stream, false};
+    Stopwatch untimed;
     for (size_t f = 0; f < F; ++f) {
         RC(launch_tables(s, dy + f * bm_in, dx + f * bm_in, dz + f * bm_in));
         const bool first = f == 0 && !resume;

@@ -35,14 +35,15 @@
 // the columns were split, or the batch. The window is worked off in bands of
 // whole tile rows that bound the partial buffer.
 //
-// Two hosts drive the kernels. The one-shot (slm_farfield_zoom) creates and
-// frees everything per call and runs hologram by hologram. The resident zoom
-// (slm_zoom_*; DESIGN.md section 3, "Resident zoom") keeps stream, buffers and
-// tables, takes a group of holograms through each launch (a window per
-// hologram if asked), takes a correction mask off in the field pass, and reads
-// the frames of a sequence in place (seq_frames.hpp), ordered with the
-// sequence's stream by events in both directions. By the accumulation rule
-// above neither the group, the band nor the split moves a bit.
+// One host drives the kernels: the resident zoom (slm_zoom_*; DESIGN.md
+// section 3, "Resident zoom"). It keeps stream, buffers and tables, takes a
+// group of holograms through each launch (a window per hologram if asked),
+// takes a correction mask off in the field pass, and reads the frames of a
+// sequence in place (seq_frames.hpp), ordered with the sequence's stream by
+// events in both directions. By the accumulation rule above neither the group,
+// the band nor the split moves a bit. The one-shot (slm_farfield_zoom) is a
+// resident zoom of one hologram, created and destroyed by the call, that the
+// holograms of the batch pass through one after the other.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -341,54 +342,43 @@ __global__ void __launch_bounds__(256) zoom_fold_kernel(FoldParams p) {
     }
 }
 
-int grid_for(long long n) { return (int)std::min<long long>(8192, (n + 255) / 256); }
 int padded(int n) { return (n + kTile - 1) / kTile * kTile; }
+
+}  // namespace
 
 using slm::DevBuf;
 using slm::fail;
+using slm::grid_for;
 
-// begin / end event pairs around the kernels of each class (events are kept and used again)
-struct Stopwatch {
-    std::vector<hipEvent_t> ev;
-    std::vector<int> cls;  // pair k is ev[2 k], ev[2 k + 1], of class cls[k]
-    size_t used = 0;
-    bool timed = false;
-    ~Stopwatch() {
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    }
-    void reset(bool on) {
-        timed = on;
-        used = 0;
-        cls.clear();
-    }
-    int mark(hipStream_t st) {
-        if (used == ev.size()) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(hipEventCreate(&e));
-            ev.push_back(e);
-        }
-        HIP_TRY(hipEventRecord(ev[used++], st));
-        return 0;
-    }
-    int begin(int c, hipStream_t st) {
-        if (!timed) return 0;
-        cls.push_back(c);
-        return mark(st);
-    }
-    int end(hipStream_t st) { return timed ? mark(st) : 0; }
-    // after the stream has been waited for
-    int read(double* kernel_us) const {
-        for (int c = 0; c < SLM_ZOOM_NUM_KERNEL_CLASSES; ++c) kernel_us[c] = 0.0;
-        for (size_t k = 0; k < cls.size(); ++k) {
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]));
-            kernel_us[cls[k]] += 1e3 * ms;
-        }
-        return 0;
-    }
+// ---- the resident zoom ----------------------------------------------------
+// Stream, buffers and tables stay with the handle; a run enqueues groups of
+// holograms back to back and returns, slm_zoom_read waits.
+struct slm_zoom {
+    int B = 0, H = 0, W = 0, max_ny = 0, max_nx = 0;
+    size_t cols_cap = 0, rows_cap = 0;  // the partial buffers of a band of product 2 and of a split product 1, at most
+    hipStream_t stream = nullptr;
+    hipEvent_t frames_written = nullptr, frames_read = nullptr;  // the two orderings with a sequence's stream
+    hipEvent_t levels_landed = nullptr;                          // the last upload from level_host
+    DevBuf<float> ain;
+    DevBuf<double> mask, level_t, origins;  // origins: y0 [B], x0 [B], z [B]
+    DevBuf<float2> levels, px, py, field, r, partial;
+    DevBuf<uint8_t> holo;
+    DevBuf<float> intensity;
+    DevBuf<double2> v;
+    // the level tables, their pinned source and its event come with the first run on levels
+    void* level_host = nullptr;  // pinned: float2 [256], then double [256]
+    double level_ct2pi = 0.0;    // what the level tables on the device were built for (0: nothing)
+    bool ain_set = false, mask_set = false, window_set = false, per_hologram = false, timed = false;
+    int ny = 0, nx = 0;
+    // the last run
+    bool ran = false, ran_field = false, ran_timed = false;
+    int ran_count = 0, ran_ny = 0, ran_nx = 0, groups = 0, bands = 0, split_launches = 0;
+    slm::Stopwatch watch, table_watch;  // the last run's kernels; the last window's two table launches
 };
 
-// ---- argument checks, shared by the one-shot and the handle ---------------
+namespace {
+
+// ---- argument checks, shared by the handle's entry points and the one-shot --
 int check_kind(int kind) {
     if (kind != SLM_ZOOM_PHASE_F32 && kind != SLM_ZOOM_LEVELS_U8) return fail(SLM_ERR_ARG, "unknown kind %d", kind);
     return 0;
@@ -403,7 +393,11 @@ int check_samples(int ny, int nx) {
         return fail(SLM_ERR_ARG, "a window has 1 .. %d samples per side, got %d x %d", kMaxSamples, ny, nx);
     return 0;
 }
-int check_pitch(double dy, double dx) {
+// the origins and defocus of `windows` windows and their pitch: finite, the pitch positive
+int check_positions(int windows, const double* y0, const double* x0, const double* z, double dy, double dx) {
+    bool finite = std::isfinite(dy) && std::isfinite(dx);
+    for (int i = 0; i < windows; ++i) finite = finite && std::isfinite(y0[i]) && std::isfinite(x0[i]) && std::isfinite(z[i]);
+    if (!finite) return fail(SLM_ERR_ARG, "the window's origin, pitch and defocus must be finite");
     if (!(dy > 0.0) || !(dx > 0.0)) return fail(SLM_ERR_ARG, "the pitch must be positive, got %g x %g", dy, dx);
     return 0;
 }
@@ -411,40 +405,6 @@ int check_ct2pi(int kind, double ct2pi) {
     if (kind == SLM_ZOOM_LEVELS_U8 && (!(ct2pi > 0.0) || !std::isfinite(ct2pi)))
         return fail(SLM_ERR_ARG, "ct2pi must be finite and positive, got %g", ct2pi);
     return 0;
-}
-int check_ain(const float* ain, size_t holo) {
-    if (!ain) return 0;
-    double sum = 0.0;
-    for (size_t i = 0; i < holo; ++i) {
-        if (!std::isfinite(ain[i])) return fail(SLM_ERR_ARG, "a_in has a non-finite entry");
-        sum += (double)ain[i] * (double)ain[i];
-    }
-    if (!(sum > 0.0)) return fail(SLM_ERR_ARG, "a_in is zero everywhere");
-    return 0;
-}
-const char kNotFinite[] = "the window's origin, pitch and defocus must be finite";
-
-int check_args(const void* hologram, int kind, int batch, int height, int width, const float* ain, double ct2pi,
-               double y0, double x0, double dy, double dx, int ny, int nx, double z, const float* intensity) {
-    if (!hologram || !intensity) return fail(SLM_ERR_ARG, "null argument");
-    RC(check_kind(kind));
-    if (batch < 1) return fail(SLM_ERR_ARG, "batch must be positive, got %d", batch);
-    RC(check_sides(height, width));
-    RC(check_samples(ny, nx));
-    if (!std::isfinite(y0) || !std::isfinite(x0) || !std::isfinite(dy) || !std::isfinite(dx) || !std::isfinite(z))
-        return fail(SLM_ERR_ARG, "%s", kNotFinite);
-    RC(check_pitch(dy, dx));
-    RC(check_ct2pi(kind, ct2pi));
-    return check_ain(ain, (size_t)height * width);
-}
-
-// the 256 level phases t = 2 pi level / ct2pi and their u, evaluated in float64 on the host
-void level_tables(double ct2pi, float2* levels, double* level_t) {
-    for (int v = 0; v < 256; ++v) {
-        const double t = kTwoPi * (double)v / ct2pi;
-        levels[v] = make_float2((float)std::cos(t), (float)std::sin(t));
-        if (level_t) level_t[v] = t;
-    }
 }
 
 int launch_table(hipStream_t st, float2* out, int windows, int N, int count, int padded_count, const double* pos0s,
@@ -456,202 +416,89 @@ int launch_table(hipStream_t st, float2* out, int windows, int N, int count, int
 }
 
 // ---- one group of holograms through the five kernels ----------------------
-// What a run works on: the device buffers, the window and how the work is cut.
-struct Pass {
-    hipStream_t st;
-    Stopwatch* watch;
-    int H, W, ny, nx, nyp, nxp, kind;
-    const float* ain;
-    const double* mask;
-    const float2* levels;
-    const double* level_t;
-    const float2 *px, *py;         // the tables of hologram 0 of the run
-    size_t px_stride, py_stride;   // 0: one window for all
-    float2 *field, *r, *partial;   // sized for one group
-    int band_rows;
-    size_t rows_partial_bytes;     // the split of product 1 fits these
+// How a run is cut: the padded window, the band, and the tables' strides (0: one window for all).
+struct Cut {
+    int kind, nyp, nxp, band_rows;
+    size_t px_stride, py_stride;
 };
 
 // product 1 of `n` holograms in one launch splits its columns if the launch's output tiles are few
-bool splits_rows(const Pass& q, int n) {
-    const int row_tiles = (q.H + kTile - 1) / kTile, wchunks = (q.W + kChunk - 1) / kChunk;
-    const size_t r_bytes = (size_t)q.H * q.nxp * sizeof(float2);
+bool splits_rows(const slm_zoom* zm, const Cut& q, int n) {
+    const int row_tiles = (zm->H + kTile - 1) / kTile, wchunks = (zm->W + kChunk - 1) / kChunk;
+    const size_t r_bytes = (size_t)zm->H * q.nxp * sizeof(float2);
     return wchunks > 1 && (long long)n * row_tiles * (q.nxp / kTile) < kSplitBelowWaves &&
-           (size_t)n * wchunks * r_bytes <= q.rows_partial_bytes;
+           (size_t)n * wchunks * r_bytes <= zm->rows_cap;
 }
 
 // `n` holograms at `holo` (device, [n][H][W]), the first of them hologram `first` of the run: the field, R,
-// and band by band V and I into intensity / v, which hold [ny][nx] per hologram `out_stride` elements
-// apart and begin at the group's first hologram. `after_band`, if given, runs after each band's fold
-// (the one-shot copies the band out there). Everything is enqueued; nothing waits.
-template <typename AfterBand>
-int enqueue_group(const Pass& q, const void* holo, int first, int n, float* intensity, double2* v, size_t out_stride,
-                  bool band_outputs, int* split_launches, AfterBand after_band) {
-    const hipStream_t st = q.st;
-    const long long holo_n = (long long)q.H * q.W;
-    const int chunks = (q.H + kChunk - 1) / kChunk, wchunks = (q.W + kChunk - 1) / kChunk;
-    const int row_tiles = (q.H + kTile - 1) / kTile, sample_groups = (q.nxp / kTile + kWaves - 1) / kWaves;
+// and band by band V and I into the run's outputs, which hold the whole window of every hologram (a band's
+// fold enters them at its row j0). Everything is enqueued; nothing waits.
+int enqueue_group(slm_zoom* zm, const Cut& q, const void* holo, int first, int n, bool want_field) {
+    const hipStream_t st = zm->stream;
+    const int H = zm->H, W = zm->W, ny = zm->ny, nx = zm->nx;
+    const long long holo_n = (long long)H * W;
+    const size_t window = (size_t)ny * nx;
+    const int chunks = (H + kChunk - 1) / kChunk, wchunks = (W + kChunk - 1) / kChunk;
+    const int row_tiles = (H + kTile - 1) / kTile, sample_groups = (q.nxp / kTile + kWaves - 1) / kWaves;
+    float* intensity = zm->intensity.p + first * window;
+    double2* v = want_field ? zm->v.p + first * window : nullptr;
 
-    RC(q.watch->begin(SLM_ZOOM_KERNEL_FIELD, st));
-    const FieldParams fp{holo, q.ain, q.mask, q.levels, q.level_t, q.field, holo_n, q.kind};
+    RC(zm->watch.begin(SLM_ZOOM_KERNEL_FIELD, st));
+    const FieldParams fp{holo, zm->ain_set ? zm->ain.p : nullptr, zm->mask_set ? zm->mask.p : nullptr, zm->levels.p,
+                         zm->level_t.p, zm->field.p, holo_n, q.kind};
     hipLaunchKernelGGL(zoom_field_kernel, dim3(grid_for(holo_n), n), dim3(256), 0, st, fp);
     HIP_TRY(hipGetLastError());
-    RC(q.watch->end(st));
+    RC(zm->watch.end(st));
 
-    RC(q.watch->begin(SLM_ZOOM_KERNEL_ROWS, st));
-    const bool split = splits_rows(q, n);
+    RC(zm->watch.begin(SLM_ZOOM_KERNEL_ROWS, st));
+    const bool split = splits_rows(zm, q, n);
     const int units = split ? wchunks : 1;
-    const RowsParams rp{q.field, q.px + (size_t)first * q.px_stride, split ? q.partial : q.r, q.px_stride, q.H, q.W,
-                        q.nxp, split ? kChunk : wchunks * kChunk, units};
+    const RowsParams rp{zm->field.p, zm->px.p + (size_t)first * q.px_stride, split ? zm->partial.p : zm->r.p,
+                        q.px_stride, H, W, q.nxp, split ? kChunk : wchunks * kChunk, units};
     hipLaunchKernelGGL(zoom_rows_kernel, dim3(sample_groups, row_tiles, n * units), dim3(kThreads), 0, st, rp);
     HIP_TRY(hipGetLastError());
     if (split) {
-        const long long r_el = (long long)q.H * q.nxp;
-        hipLaunchKernelGGL(zoom_rows_fold_kernel, dim3(grid_for(r_el), n), dim3(256), 0, st, q.partial, q.r, wchunks,
-                           r_el);
+        const long long r_el = (long long)H * q.nxp;
+        hipLaunchKernelGGL(zoom_rows_fold_kernel, dim3(grid_for(r_el), n), dim3(256), 0, st, zm->partial.p, zm->r.p,
+                           wchunks, r_el);
         HIP_TRY(hipGetLastError());
-        if (split_launches) ++*split_launches;
+        ++zm->split_launches;
     }
-    RC(q.watch->end(st));
+    RC(zm->watch.end(st));
 
-    for (int j0 = 0; j0 < q.ny; j0 += q.band_rows) {
-        const int tile_rows = std::min(q.band_rows, q.nyp - j0), rows = std::min(q.band_rows, q.ny - j0);
-        RC(q.watch->begin(SLM_ZOOM_KERNEL_COLS, st));
-        const ColsParams cp{q.py + (size_t)first * q.py_stride, q.r, q.partial, q.py_stride, q.H, q.nyp, q.nxp, j0,
-                            q.band_rows, chunks};
+    for (int j0 = 0; j0 < ny; j0 += q.band_rows) {
+        const int tile_rows = std::min(q.band_rows, q.nyp - j0), rows = std::min(q.band_rows, ny - j0);
+        RC(zm->watch.begin(SLM_ZOOM_KERNEL_COLS, st));
+        const ColsParams cp{zm->py.p + (size_t)first * q.py_stride, zm->r.p, zm->partial.p, q.py_stride, H, q.nyp,
+                            q.nxp, j0, q.band_rows, chunks};
         hipLaunchKernelGGL(zoom_cols_kernel, dim3(sample_groups, tile_rows / kTile, n * chunks), dim3(kThreads), 0, st,
                            cp);
         HIP_TRY(hipGetLastError());
-        // outputs that hold one band start at the band; outputs that hold the window are entered at row j0
-        const size_t at = band_outputs ? 0 : (size_t)j0 * q.nx;
-        const FoldParams fo{q.partial, intensity + at, v ? v + at : nullptr, out_stride, chunks, q.band_rows, rows,
-                            q.nx, q.nxp};
-        hipLaunchKernelGGL(zoom_fold_kernel, dim3(grid_for((long long)rows * q.nx), n), dim3(256), 0, st, fo);
+        const size_t at = (size_t)j0 * nx;
+        const FoldParams fo{zm->partial.p, intensity + at, v ? v + at : nullptr, window, chunks, q.band_rows, rows, nx,
+                            q.nxp};
+        hipLaunchKernelGGL(zoom_fold_kernel, dim3(grid_for((long long)rows * nx), n), dim3(256), 0, st, fo);
         HIP_TRY(hipGetLastError());
-        RC(q.watch->end(st));
-        RC(after_band(j0, rows));
+        RC(zm->watch.end(st));
     }
     return 0;
 }
 
 // bytes of the partial buffer a group of n holograms needs
-size_t partial_bytes(const Pass& q, int n) {
-    const int chunks = (q.H + kChunk - 1) / kChunk, wchunks = (q.W + kChunk - 1) / kChunk;
+size_t partial_bytes(const slm_zoom* zm, const Cut& q, int n) {
+    const int chunks = (zm->H + kChunk - 1) / kChunk, wchunks = (zm->W + kChunk - 1) / kChunk;
     const size_t cols = (size_t)n * chunks * q.band_rows * q.nxp * sizeof(float2);
-    const size_t rows = splits_rows(q, n) ? (size_t)n * wchunks * q.H * q.nxp * sizeof(float2) : 0;
+    const size_t rows = splits_rows(zm, q, n) ? (size_t)n * wchunks * zm->H * q.nxp * sizeof(float2) : 0;
     return std::max(cols, rows);
 }
 
-// the band of one hologram: whole tile rows whose chunk results fit `cap` (one tile row always fits)
+// the band of n holograms: whole tile rows whose chunk results fit `cap` (one tile row always fits)
 int band_rows_for(int H, int nyp, int nxp, size_t cap, int n) {
     const size_t row_bytes = (size_t)n * ((H + kChunk - 1) / kChunk) * nxp * sizeof(float2);
     return (int)std::min<size_t>(nyp, std::max<size_t>(kTile, cap / row_bytes / kTile * kTile));
 }
 
-// ---- the one-shot ---------------------------------------------------------
-// the call's stream and buffers, all released when it returns
-struct OneShot {
-    hipStream_t stream = nullptr;
-    DevBuf<float> ain;
-    DevBuf<float2> levels, px, py, field, r, partial;
-    DevBuf<uint8_t> holo;
-    DevBuf<float> intensity;
-    DevBuf<double2> v;
-    Stopwatch watch;
-    ~OneShot() {
-        if (stream) {
-            (void)hipStreamSynchronize(stream);
-            (void)hipStreamDestroy(stream);
-        }
-    }
-};
-
-int zoom_run(OneShot& zm, const void* hologram, int kind, int batch, int H, int W, const float* ain, double ct2pi,
-             double y0, double x0, double dy, double dx, int ny, int nx, double z, float* intensity, double* field) {
-    HIP_TRY(hipStreamCreateWithFlags(&zm.stream, hipStreamNonBlocking));
-    const hipStream_t st = zm.stream;
-    const int nxp = padded(nx), nyp = padded(ny);
-    const size_t holo = (size_t)H * W, el = kind == SLM_ZOOM_LEVELS_U8 ? 1 : sizeof(float);
-    Pass q{st, &zm.watch, H, W, ny, nx, nyp, nxp, kind};
-    q.band_rows = band_rows_for(H, nyp, nxp, kPartialBytes, 1);
-    q.rows_partial_bytes = kRowsPartialBytes;
-
-    if (ain) RC(zm.ain.need(holo * sizeof(float), st));
-    if (kind == SLM_ZOOM_LEVELS_U8) RC(zm.levels.need(256 * sizeof(float2), st));
-    RC(zm.px.need((size_t)W * nxp * sizeof(float2), st));
-    RC(zm.py.need((size_t)H * nyp * sizeof(float2), st));
-    RC(zm.holo.need(holo * el, st));
-    RC(zm.field.need(holo * sizeof(float2), st));
-    RC(zm.r.need((size_t)H * nxp * sizeof(float2), st));
-    RC(zm.partial.need(partial_bytes(q, 1), st));
-    RC(zm.intensity.need((size_t)q.band_rows * nx * sizeof(float), st));
-    if (field) RC(zm.v.need((size_t)q.band_rows * nx * sizeof(double2), st));
-
-    if (ain) RC(slm::copy_sync(zm.ain.p, ain, holo * sizeof(float), hipMemcpyHostToDevice, st));
-    if (kind == SLM_ZOOM_LEVELS_U8) {
-        float2 levels[256];
-        level_tables(ct2pi, levels, nullptr);
-        RC(slm::copy_sync(zm.levels.p, levels, sizeof(levels), hipMemcpyHostToDevice, st));
-    }
-    RC(zm.watch.begin(SLM_ZOOM_KERNEL_TABLES, st));
-    RC(launch_table(st, zm.px.p, 1, W, nx, nxp, nullptr, nullptr, x0, dx, z));
-    RC(launch_table(st, zm.py.p, 1, H, ny, nyp, nullptr, nullptr, y0, dy, z));
-    RC(zm.watch.end(st));
-    q.ain = ain ? zm.ain.p : nullptr;
-    q.levels = zm.levels.p;
-    q.px = zm.px.p;
-    q.py = zm.py.p;
-    q.field = zm.field.p;
-    q.r = zm.r.p;
-    q.partial = zm.partial.p;
-
-    for (int b = 0; b < batch; ++b) {
-        RC(slm::copy_sync(zm.holo.p, static_cast<const uint8_t*>(hologram) + (size_t)b * holo * el, holo * el,
-                          hipMemcpyHostToDevice, st));
-        RC(enqueue_group(q, zm.holo.p, 0, 1, zm.intensity.p, field ? zm.v.p : nullptr, 0, true, nullptr,
-                         [&](int j0, int rows) {
-                             const size_t at = ((size_t)b * ny + j0) * nx, n = (size_t)rows * nx;
-                             RC(slm::copy_sync(intensity + at, zm.intensity.p, n * sizeof(float),
-                                               hipMemcpyDeviceToHost, st));
-                             if (field)
-                                 RC(slm::copy_sync(field + 2 * at, zm.v.p, n * sizeof(double2), hipMemcpyDeviceToHost,
-                                                   st));
-                             return 0;
-                         }));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    return 0;
-}
-
-}  // namespace
-
-// ---- the resident zoom ----------------------------------------------------
-// Stream, buffers and tables stay with the handle; a run enqueues groups of
-// holograms back to back and returns, slm_zoom_read waits.
-struct slm_zoom {
-    int B = 0, H = 0, W = 0, max_ny = 0, max_nx = 0;
-    size_t cols_cap = kPartialBytes, rows_cap = kRowsPartialBytes;  // $SLM_ZOOM_PARTIAL_BYTES replaces both
-    hipStream_t stream = nullptr;
-    hipEvent_t frames_written = nullptr, frames_read = nullptr;  // the two orderings with a sequence's stream
-    hipEvent_t levels_landed = nullptr;                          // the last upload from level_host
-    DevBuf<float> ain;
-    DevBuf<double> mask, level_t, origins;  // origins: y0 [B], x0 [B], z [B]
-    DevBuf<float2> levels, px, py, field, r, partial;
-    DevBuf<uint8_t> holo;
-    DevBuf<float> intensity;
-    DevBuf<double2> v;
-    void* level_host = nullptr;  // pinned: float2 [256], then double [256]
-    double level_ct2pi = 0.0;    // what the level tables on the device were built for (0: nothing)
-    bool ain_set = false, mask_set = false, window_set = false, per_hologram = false, timed = false;
-    int ny = 0, nx = 0;
-    // the last run
-    bool ran = false, ran_field = false, ran_timed = false;
-    int ran_count = 0, ran_ny = 0, ran_nx = 0, groups = 0, bands = 0, split_launches = 0;
-    Stopwatch watch;
-};
-
-namespace {
-
+// ---- the handle's own host code -------------------------------------------
 constexpr int kMaxBatch = 1024;
 // the field of one group, at most: with windows of a few tiles the partial caps alone would admit hundreds
 // of holograms of any size
@@ -665,6 +512,101 @@ void zoom_free(slm_zoom* zm) {
     if (zm->level_host) (void)hipHostFree(zm->level_host);
     if (zm->stream) (void)hipStreamDestroy(zm->stream);
     delete zm;
+}
+
+// a handle of checked sizes with the two caps of its partial buffers
+int zoom_create(int batch, int height, int width, int max_ny, int max_nx, size_t cols_cap, size_t rows_cap,
+                slm_zoom** out) {
+    RC(slm::ensure_device());
+    slm_zoom* zm = new slm_zoom;
+    zm->B = batch;
+    zm->H = height;
+    zm->W = width;
+    zm->max_ny = max_ny;
+    zm->max_nx = max_nx;
+    zm->cols_cap = cols_cap;
+    zm->rows_cap = rows_cap;
+    int rc = [&]() {
+        HIP_TRY(hipStreamCreateWithFlags(&zm->stream, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&zm->frames_written, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&zm->frames_read, hipEventDisableTiming));
+        return 0;
+    }();
+    if (rc) {
+        zoom_free(zm);
+        return rc;
+    }
+    *out = zm;
+    return 0;
+}
+
+// a checked a_in (nullptr = ones)
+int zoom_put_ain(slm_zoom* zm, const float* ain) {
+    const size_t holo = (size_t)zm->H * zm->W;
+    RC(slm::ensure_device());
+    zm->ain_set = false;
+    if (!ain) return 0;
+    RC(zm->ain.need(holo * sizeof(float), zm->stream));
+    RC(slm::copy_sync(zm->ain.p, ain, holo * sizeof(float), hipMemcpyHostToDevice, zm->stream));
+    zm->ain_set = true;
+    return 0;
+}
+
+// a checked window: its tables
+int zoom_put_window(slm_zoom* zm, int per_hologram, const double* y0, const double* x0, const double* z, double dy,
+                    double dx, int ny, int nx) {
+    RC(slm::ensure_device());
+    const hipStream_t st = zm->stream;
+    const int windows = per_hologram ? zm->B : 1, nxp = padded(nx), nyp = padded(ny);
+    zm->window_set = false;
+    RC(zm->px.need((size_t)windows * zm->W * nxp * sizeof(float2), st));
+    RC(zm->py.need((size_t)windows * zm->H * nyp * sizeof(float2), st));
+    const double *dev_y0 = nullptr, *dev_x0 = nullptr, *dev_z = nullptr;
+    if (per_hologram) {
+        RC(zm->origins.need(3 * (size_t)windows * sizeof(double), st));
+        dev_y0 = zm->origins.p;
+        dev_x0 = dev_y0 + windows;
+        dev_z = dev_x0 + windows;
+        const size_t bytes = (size_t)windows * sizeof(double);
+        RC(slm::copy_sync(zm->origins.p, y0, bytes, hipMemcpyHostToDevice, st));
+        RC(slm::copy_sync(zm->origins.p + windows, x0, bytes, hipMemcpyHostToDevice, st));
+        RC(slm::copy_sync(zm->origins.p + 2 * windows, z, bytes, hipMemcpyHostToDevice, st));
+    }
+    zm->table_watch.reset(zm->timed);
+    RC(zm->table_watch.begin(SLM_ZOOM_KERNEL_TABLES, st));
+    RC(launch_table(st, zm->px.p, windows, zm->W, nx, nxp, dev_x0, dev_z, x0[0], dx, z[0]));
+    RC(launch_table(st, zm->py.p, windows, zm->H, ny, nyp, dev_y0, dev_z, y0[0], dy, z[0]));
+    RC(zm->table_watch.end(st));
+    zm->per_hologram = per_hologram != 0;
+    zm->ny = ny;
+    zm->nx = nx;
+    zm->window_set = true;
+    return 0;
+}
+
+// the 256 level phases t = 2 pi level / ct2pi and their u, evaluated in float64 on the host and uploaded
+int upload_levels(slm_zoom* zm, double ct2pi) {
+    const hipStream_t st = zm->stream;
+    if (!zm->levels_landed) HIP_TRY(hipEventCreateWithFlags(&zm->levels_landed, hipEventDisableTiming));
+    RC(zm->levels.need(256 * sizeof(float2), st));
+    RC(zm->level_t.need(256 * sizeof(double), st));
+    if (!zm->level_host)
+        HIP_TRY(hipHostMalloc(&zm->level_host, 256 * (sizeof(float2) + sizeof(double)), hipHostMallocDefault));
+    // the pinned tables are written only after their last upload has left them
+    HIP_TRY(hipEventSynchronize(zm->levels_landed));
+    float2* levels = static_cast<float2*>(zm->level_host);
+    double* level_t = reinterpret_cast<double*>(levels + 256);
+    for (int v = 0; v < 256; ++v) {
+        const double t = kTwoPi * (double)v / ct2pi;
+        levels[v] = make_float2((float)std::cos(t), (float)std::sin(t));
+        level_t[v] = t;
+    }
+    zm->level_ct2pi = 0.0;
+    HIP_TRY(hipMemcpyAsync(zm->levels.p, levels, 256 * sizeof(float2), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(zm->level_t.p, level_t, 256 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(zm->levels_landed, st));
+    zm->level_ct2pi = ct2pi;
+    return 0;
 }
 
 // holograms per group and the band of a run of `count`: as many holograms as keep the second product's
@@ -693,50 +635,24 @@ int zoom_enqueue(slm_zoom* zm, const void* dev_holo, int kind, int count, double
     const size_t holo = (size_t)zm->H * zm->W, el = kind == SLM_ZOOM_LEVELS_U8 ? 1 : sizeof(float);
     const size_t window = (size_t)zm->ny * zm->nx;
     zm->ran = false;
-    if (kind == SLM_ZOOM_LEVELS_U8 && ct2pi != zm->level_ct2pi) {
-        // the pinned tables are written only after their last upload has left them
-        HIP_TRY(hipEventSynchronize(zm->levels_landed));
-        float2* levels = static_cast<float2*>(zm->level_host);
-        double* level_t = reinterpret_cast<double*>(levels + 256);
-        level_tables(ct2pi, levels, level_t);
-        zm->level_ct2pi = 0.0;
-        HIP_TRY(hipMemcpyAsync(zm->levels.p, levels, 256 * sizeof(float2), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(zm->level_t.p, level_t, 256 * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipEventRecord(zm->levels_landed, st));
-        zm->level_ct2pi = ct2pi;
-    }
+    if (kind == SLM_ZOOM_LEVELS_U8 && ct2pi != zm->level_ct2pi) RC(upload_levels(zm, ct2pi));
     int group = 1, band_rows = kTile;
     cut_run(zm, count, &group, &band_rows);
-    zm->watch.reset(zm->timed);
-    Pass q{st, &zm->watch, zm->H, zm->W, zm->ny, zm->nx, nyp, nxp, kind};
-    q.band_rows = band_rows;
-    q.rows_partial_bytes = zm->rows_cap;
-    q.px_stride = zm->per_hologram ? (size_t)zm->W * nxp : 0;
-    q.py_stride = zm->per_hologram ? (size_t)zm->H * nyp : 0;
+    const Cut q{kind, nyp, nxp, band_rows, zm->per_hologram ? (size_t)zm->W * nxp : 0,
+                zm->per_hologram ? (size_t)zm->H * nyp : 0};
     const int last = count - (count - 1) / group * group;  // the last group's holograms
     RC(zm->field.need((size_t)group * holo * sizeof(float2), st));
     RC(zm->r.need((size_t)group * zm->H * nxp * sizeof(float2), st));
-    RC(zm->partial.need(std::max(partial_bytes(q, group), partial_bytes(q, last)), st));
+    RC(zm->partial.need(std::max(partial_bytes(zm, q, group), partial_bytes(zm, q, last)), st));
     RC(zm->intensity.need((size_t)count * window * sizeof(float), st));
     if (want_field) RC(zm->v.need((size_t)count * window * sizeof(double2), st));
-    q.ain = zm->ain_set ? zm->ain.p : nullptr;
-    q.mask = zm->mask_set ? zm->mask.p : nullptr;
-    q.levels = zm->levels.p;
-    q.level_t = zm->level_t.p;
-    q.px = zm->px.p;
-    q.py = zm->py.p;
-    q.field = zm->field.p;
-    q.r = zm->r.p;
-    q.partial = zm->partial.p;
 
+    zm->watch.reset(zm->timed);
     zm->groups = zm->split_launches = 0;
     zm->bands = (zm->ny + band_rows - 1) / band_rows;
-    for (int first = 0; first < count; first += group, ++zm->groups) {
-        const int n = std::min(group, count - first);
-        RC(enqueue_group(q, static_cast<const uint8_t*>(dev_holo) + (size_t)first * holo * el, first, n,
-                         zm->intensity.p + (size_t)first * window, want_field ? zm->v.p + (size_t)first * window : nullptr,
-                         window, false, &zm->split_launches, [](int, int) { return 0; }));
-    }
+    for (int first = 0; first < count; first += group, ++zm->groups)
+        RC(enqueue_group(zm, q, static_cast<const uint8_t*>(dev_holo) + (size_t)first * holo * el, first,
+                         std::min(group, count - first), want_field != 0));
     if (writer) {
         // the source's next write to its frames comes after this run's reads
         HIP_TRY(hipEventRecord(zm->frames_read, st));
@@ -783,16 +699,43 @@ int zoom_run_frames(slm_zoom* zm, const slm::SeqFrames& src, const char* what, i
 
 extern "C" {
 
+// The one-shot: a resident zoom of one hologram that lives for the call. Everything is checked before the
+// handle is created; the holograms of the batch go through it one after the other.
 int slm_farfield_zoom_timed(const void* hologram, int kind, int batch, int height, int width, const float* ain,
                             double ct2pi, double y0, double x0, double dy, double dx, int ny, int nx, double z,
                             float* intensity, double* field, double* kernel_us) {
-    RC(check_args(hologram, kind, batch, height, width, ain, ct2pi, y0, x0, dy, dx, ny, nx, z, intensity));
-    RC(slm::ensure_device());
-    OneShot zm;
-    zm.watch.reset(kernel_us != nullptr);
-    RC(zoom_run(zm, hologram, kind, batch, height, width, ain, ct2pi, y0, x0, dy, dx, ny, nx, z, intensity, field));
-    if (kernel_us) RC(zm.watch.read(kernel_us));
-    return 0;
+    if (!hologram || !intensity) return fail(SLM_ERR_ARG, "null argument");
+    RC(check_kind(kind));
+    if (batch < 1) return fail(SLM_ERR_ARG, "batch must be positive, got %d", batch);
+    RC(check_sides(height, width));
+    RC(check_samples(ny, nx));
+    RC(check_positions(1, &y0, &x0, &z, dy, dx));
+    RC(check_ct2pi(kind, ct2pi));
+    const size_t holo = (size_t)height * width, window = (size_t)ny * nx;
+    RC(slm::check_ain(ain, holo, nullptr));
+    slm_zoom* zm = nullptr;
+    RC(zoom_create(1, height, width, ny, nx, kPartialBytes, kRowsPartialBytes, &zm));  // never the environment's caps
+    const int rc = [&]() {
+        constexpr int kClasses = SLM_ZOOM_NUM_KERNEL_CLASSES;
+        double us[kClasses], total[kClasses] = {};
+        zm->timed = kernel_us != nullptr;
+        RC(zoom_put_ain(zm, ain));
+        RC(zoom_put_window(zm, 0, &y0, &x0, &z, dy, dx, ny, nx));
+        const size_t holo_bytes = holo * (kind == SLM_ZOOM_LEVELS_U8 ? 1 : sizeof(float));
+        for (int b = 0; b < batch; ++b) {
+            RC(slm_zoom_run(zm, static_cast<const uint8_t*>(hologram) + b * holo_bytes, kind, 1, ct2pi,
+                            field != nullptr));
+            RC(slm_zoom_read(zm, intensity + b * window, field ? field + 2 * b * window : nullptr,
+                             kernel_us ? us : nullptr));
+            for (int c = 0; kernel_us && c < kClasses; ++c) total[c] += us[c];
+        }
+        if (!kernel_us) return 0;
+        RC(zm->table_watch.read(us, kClasses));  // the reads above have waited for the stream
+        for (int c = 0; c < kClasses; ++c) kernel_us[c] = total[c] + us[c];
+        return 0;
+    }();
+    zoom_free(zm);
+    return rc;
 }
 
 int slm_farfield_zoom(const void* hologram, int kind, int batch, int height, int width, const float* ain, double ct2pi,
@@ -809,38 +752,15 @@ int slm_zoom_create(int batch, int height, int width, int max_ny, int max_nx, sl
         return fail(SLM_ERR_ARG, "a zoom handle takes 1 .. %d holograms per run, got %d", kMaxBatch, batch);
     RC(check_sides(height, width));
     RC(check_samples(max_ny, max_nx));
-    size_t cap = 0;
+    size_t cols_cap = kPartialBytes, rows_cap = kRowsPartialBytes;
     if (const char* env = std::getenv("SLM_ZOOM_PARTIAL_BYTES")) {
         char* end = nullptr;
         const long long v = std::strtoll(env, &end, 10);
         if (end == env || *end || v < 1)
             return fail(SLM_ERR_ARG, "$SLM_ZOOM_PARTIAL_BYTES must be a positive whole number, got \"%s\"", env);
-        cap = (size_t)v;
+        cols_cap = rows_cap = (size_t)v;
     }
-    RC(slm::ensure_device());
-    slm_zoom* zm = new slm_zoom;
-    zm->B = batch;
-    zm->H = height;
-    zm->W = width;
-    zm->max_ny = max_ny;
-    zm->max_nx = max_nx;
-    if (cap) zm->cols_cap = zm->rows_cap = cap;
-    int rc = [&]() {
-        HIP_TRY(hipStreamCreateWithFlags(&zm->stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&zm->frames_written, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&zm->frames_read, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&zm->levels_landed, hipEventDisableTiming));
-        HIP_TRY(hipHostMalloc(&zm->level_host, 256 * (sizeof(float2) + sizeof(double)), hipHostMallocDefault));
-        RC(zm->levels.need(256 * sizeof(float2), zm->stream));
-        RC(zm->level_t.need(256 * sizeof(double), zm->stream));
-        return 0;
-    }();
-    if (rc) {
-        zoom_free(zm);
-        return rc;
-    }
-    *out = zm;
-    return 0;
+    return zoom_create(batch, height, width, max_ny, max_nx, cols_cap, rows_cap, out);
 }
 
 int slm_zoom_destroy(slm_zoom* zm) {
@@ -851,15 +771,8 @@ int slm_zoom_destroy(slm_zoom* zm) {
 
 int slm_zoom_set_ain(slm_zoom* zm, const float* ain) {
     if (!zm) return fail(SLM_ERR_ARG, "null zoom handle");
-    const size_t holo = (size_t)zm->H * zm->W;
-    RC(check_ain(ain, holo));
-    RC(slm::ensure_device());
-    zm->ain_set = false;
-    if (!ain) return 0;
-    RC(zm->ain.need(holo * sizeof(float), zm->stream));
-    RC(slm::copy_sync(zm->ain.p, ain, holo * sizeof(float), hipMemcpyHostToDevice, zm->stream));
-    zm->ain_set = true;
-    return 0;
+    RC(slm::check_ain(ain, (size_t)zm->H * zm->W, nullptr));
+    return zoom_put_ain(zm, ain);
 }
 
 int slm_zoom_set_mask(slm_zoom* zm, const double* mask) {
@@ -883,35 +796,8 @@ int slm_zoom_set_window(slm_zoom* zm, int per_hologram, const double* y0, const 
     if (ny > zm->max_ny || nx > zm->max_nx)
         return fail(SLM_ERR_ARG, "a window of %d x %d samples exceeds the handle's %d x %d", ny, nx, zm->max_ny,
                     zm->max_nx);
-    const int windows = per_hologram ? zm->B : 1;
-    bool finite = std::isfinite(dy) && std::isfinite(dx);
-    for (int i = 0; i < windows; ++i) finite = finite && std::isfinite(y0[i]) && std::isfinite(x0[i]) && std::isfinite(z[i]);
-    if (!finite) return fail(SLM_ERR_ARG, "%s", kNotFinite);
-    RC(check_pitch(dy, dx));
-    RC(slm::ensure_device());
-    const hipStream_t st = zm->stream;
-    const int nxp = padded(nx), nyp = padded(ny);
-    zm->window_set = false;
-    RC(zm->px.need((size_t)windows * zm->W * nxp * sizeof(float2), st));
-    RC(zm->py.need((size_t)windows * zm->H * nyp * sizeof(float2), st));
-    const double *dev_y0 = nullptr, *dev_x0 = nullptr, *dev_z = nullptr;
-    if (per_hologram) {
-        RC(zm->origins.need(3 * (size_t)windows * sizeof(double), st));
-        dev_y0 = zm->origins.p;
-        dev_x0 = dev_y0 + windows;
-        dev_z = dev_x0 + windows;
-        const size_t bytes = (size_t)windows * sizeof(double);
-        RC(slm::copy_sync(zm->origins.p, y0, bytes, hipMemcpyHostToDevice, st));
-        RC(slm::copy_sync(zm->origins.p + windows, x0, bytes, hipMemcpyHostToDevice, st));
-        RC(slm::copy_sync(zm->origins.p + 2 * windows, z, bytes, hipMemcpyHostToDevice, st));
-    }
-    RC(launch_table(st, zm->px.p, windows, zm->W, nx, nxp, dev_x0, dev_z, x0[0], dx, z[0]));
-    RC(launch_table(st, zm->py.p, windows, zm->H, ny, nyp, dev_y0, dev_z, y0[0], dy, z[0]));
-    zm->per_hologram = per_hologram != 0;
-    zm->ny = ny;
-    zm->nx = nx;
-    zm->window_set = true;
-    return 0;
+    RC(check_positions(per_hologram ? zm->B : 1, y0, x0, z, dy, dx));
+    return zoom_put_window(zm, per_hologram, y0, x0, z, dy, dx, ny, nx);
 }
 
 int slm_zoom_set_timed(slm_zoom* zm, int timed) {
@@ -951,7 +837,7 @@ int slm_zoom_read(slm_zoom* zm, float* intensity, double* field, double* kernel_
     const size_t n = (size_t)zm->ran_count * zm->ran_ny * zm->ran_nx;
     if (intensity) RC(slm::copy_sync(intensity, zm->intensity.p, n * sizeof(float), hipMemcpyDeviceToHost, zm->stream));
     if (field) RC(slm::copy_sync(field, zm->v.p, n * sizeof(double2), hipMemcpyDeviceToHost, zm->stream));
-    if (kernel_us) RC(zm->watch.read(kernel_us));
+    if (kernel_us) RC(zm->watch.read(kernel_us, SLM_ZOOM_NUM_KERNEL_CLASSES));
     return 0;
 }
 

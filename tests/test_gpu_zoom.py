@@ -277,3 +277,55 @@ def test_cli_writes_the_expected_outcome(gpu, tmp_path, monkeypatch):
             assert min(max(abs(j - wj), abs(i - wi)) for wj, wi in want) <= 1.0, (f, j, i, want)
         assert len({min(range(4), key=lambda m: abs(j - want[m][0]) + abs(i - want[m][1])) for j, i in peaks}) == 4
     mt.clear_spots()
+
+
+# ---------------------------------------------------------------------------
+# 8. the one-shot is a resident zoom of one hologram: its bands, its caps, its timing
+# ---------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_banded_one_shot(gpu):
+    """One hologram's chunk results, 5 chunks x 1312 x 1312 x 8 B = 68.9 MB, exceed
+    the 64 MB cap: the one-shot runs two bands, of 1248 and 64 rows."""
+    h, w, size, z = 1056, 300, (1300, 1300), 2e-4
+    origin, pitch = (-3.375, 2.625), 0.125  # dyadic: y0 + j dy is the same float64 in both windows
+    phase = _phase(h, w, 23)
+    big_i, big_v = gpu.farfield_zoom(phase, origin, pitch, size, z=z, return_field=True)
+    with gpu.Zoom(1, h, w, size) as zm:
+        zm.set_window(origin, pitch, size, z)
+        zm.run(phase, return_field=True)
+        got_i, got_v = zm.read()
+        assert zm.info()["bands"] == 2
+    np.testing.assert_array_equal(got_i[0], big_i)
+    np.testing.assert_array_equal(got_v[0], big_v)
+    j0, i0, sub = 1236, 37, (24, 40)  # rows 1236 .. 1259 lie across the two bands
+    sub_i, sub_v = gpu.farfield_zoom(phase, (origin[0] + j0 * pitch, origin[1] + i0 * pitch), pitch, sub, z=z,
+                                     return_field=True)
+    np.testing.assert_array_equal(sub_i, big_i[j0:j0 + sub[0], i0:i0 + sub[1]])
+    np.testing.assert_array_equal(sub_v, big_v[j0:j0 + sub[0], i0:i0 + sub[1]])
+
+
+@pytest.mark.gpu
+def test_the_environment_does_not_reach_the_one_shot(gpu, monkeypatch):
+    h, w, size = 130, 264, (96, 40)
+    holos = np.stack([_phase(h, w, 17), _phase(h, w, 18)])
+    origin, pitch, z = (-3.375, 2.625), 0.125, 2e-4
+    monkeypatch.delenv("SLM_ZOOM_PARTIAL_BYTES", raising=False)
+    want_i, want_v = gpu.farfield_zoom(holos, origin, pitch, size, z=z, return_field=True)
+    for value in ("32768", "many"):
+        monkeypatch.setenv("SLM_ZOOM_PARTIAL_BYTES", value)
+        got_i, got_v = gpu.farfield_zoom(holos, origin, pitch, size, z=z, return_field=True)
+        np.testing.assert_array_equal(got_i, want_i)
+        np.testing.assert_array_equal(got_v, want_v)
+
+
+@pytest.mark.gpu
+def test_timed_one_shot(gpu):
+    h, w, size = 45, 70, (33, 70)
+    frames = np.random.default_rng(41).integers(0, 256, (2, h, w), dtype=np.uint8)
+    origin, pitch = (-3.375, 2.625), 0.125
+    plain = gpu.farfield_zoom(frames, origin, pitch, size, ct2pi=200)
+    inten, us = gpu.farfield_zoom(frames, origin, pitch, size, ct2pi=200, timed=True)
+    print(f"zoom timed one-shot: {dict(zip(gpu.ZOOM_KERNEL_CLASS_NAMES, us))} us")
+    assert us.shape == (gpu.ZOOM_NUM_KERNEL_CLASSES,) and gpu.ZOOM_NUM_KERNEL_CLASSES == 4
+    assert np.isfinite(us).all() and (us > 0).all()
+    np.testing.assert_array_equal(inten, plain)
